@@ -11,9 +11,17 @@ exact rescoring, RCCL all-gather of candidates, exact merge, guard/fallback.
 Launch: python bench.py [--gpus N --steps K --warmup W]; for N > 1 under
 torch.distributed.run (one rank per GPU, RCCL).  Rank 0 prints ONE JSON line.
 
+A plain run does what the headline needs and no more: build the corpus, warm up, time the
+K steps, write the last step's answers (``--dump-outputs DIR``: DIR/scores.npy, DIR/ids.npy)
+and print the line (value, ms_per_step, the FILTER's roofline from HIP events inside the
+timed region).  Everything else -- the isotropic batch, ``ranks_agree`` / ``result_sha256``,
+the recall checks, ``gpu_embed_plus_search``, ``cpu_baseline``, ``cpu_oracle`` -- runs after
+the timed steps with ``--full`` only.
+
 Inputs are resident in HBM before the timed region: every rank generates its shard
 on its GPU with the counter-based generator (hiprag.synth) and all query batches
-are uploaded up front.  ``cpu_baseline`` (rank 0, N=1 only) times the reference's CPU
+are uploaded up front; both are seeded, so the same arguments give the same inputs in
+every run.  ``cpu_baseline`` (rank 0, N=1 only) times the reference's CPU
 search path (FAISS IndexFlatIP semantics = BLAS sgemm + top-k over the fp32 store, its
 per-query loop and the CPU query embedding) on a bounded row sample and scales it to the
 full corpus; ``cpu_oracle`` times the exact fp64 checker (oracle/, test infrastructure);
@@ -60,8 +68,16 @@ def parse():
     p.add_argument("--cpu-ref-rows", type=int, default=1_000_000, help="row sample of the reference-path CPU baseline")
     p.add_argument("--cpu-embed-preset", default="bge-large")
     p.add_argument("--recall-queries", type=int, default=64, help="planted and isotropic queries of the recall checks")
-    p.add_argument("--no-cpu", action="store_true", help="skip cpu_baseline, recall and the GPU embed leg (quick runs)")
-    p.add_argument("--no-embed", action="store_true", help="skip the GPU embed+search leg")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run the checks and side measurements: the isotropic batch, "
+                        "ranks_agree / result_sha256, recall against the oracle, gpu_embed_plus_search, cpu_baseline "
+                        "and cpu_oracle (off by default: a plain run sets up, warms up, times the steps and prints)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write the last timed step's answers as DIR/scores.npy (float32, "
+                        "batch x k) and DIR/ids.npy (row ids as float64, batch x k)")
+    p.add_argument("--no-cpu", action="store_true",
+                   help="with --full: skip cpu_baseline, recall and the GPU embed leg (a plain run has none of them)")
+    p.add_argument("--no-embed", action="store_true", help="with --full: skip the GPU embed+search leg")
     # (off by default: with the CUs split 48/64/96/128 : rest the pipeline measured 5.4k / 6.6k / 7.0k / 7.0k QPS
     # against 9.1k sharing every CU and 9.8k sequential -- profiles/r05_embed_cu_split.json)
     p.add_argument("--embed-cus", default="",
@@ -473,7 +489,9 @@ def main_single_process(args):
                                      f"striped over {len(devs)} shards", "rows": N, "dim": D, "batch": B, "k": K,
                          "parallelism": f"onehandle{len(devs)}", "devices": devs},
               "host_us_per_batch": host}
-    if not args.no_cpu:
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, s_dev[-1], r_dev[-1])
+    if args.full and not args.no_cpu:
         q_iso = isotropic_queries(B, D)
         qi_dev = torch.from_numpy(q_iso).to(dev)
         s_iso = torch.empty((B, K), dtype=torch.float32, device=dev)
@@ -553,6 +571,16 @@ def _protect_stdout():
         os.dup2(2, 1)
 
 
+def dump_outputs(path: str, scores, ids) -> None:
+    """--dump-outputs: what a caller of the timed path received for the LAST timed step -- the (batch, k) scores
+    (float32, as returned) and row ids (int64 on the device; every id is below 2^53, so float64 holds it exactly).
+    The inputs are seeded (--seed, the batch number), so two builds given the same arguments answer the same queries
+    over the same corpus and their files can be compared element for element."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "scores.npy"), scores.cpu().numpy().astype(np.float32))
+    np.save(os.path.join(path, "ids.npy"), ids.cpu().numpy().astype(np.float64))
+
+
 def emit(result: dict) -> None:
     print(json.dumps(result), file=_RESULT_OUT or sys.stdout, flush=True)
 
@@ -610,11 +638,13 @@ def main():
     log(f"[rank {rank}] shard rows [{start}, {stop}) built in {time.time() - t0:.1f}s")
 
     # all query batches resident in HBM up front (planted queries: realistic margins)
+    # (each batch is seeded by its number, so generating them on a few host threads gives the same queries: at
+    # ~5 ms of numpy per batch a long run's set-up would otherwise outlast its timed steps)
     n_batches = args.warmup + args.steps
-    qs = []
-    for i in range(n_batches):
-        q, _ = synth.planted_queries(args.seed, N, D, B, qseed=1000 + i)
-        qs.append(q)
+    from concurrent.futures import ThreadPoolExecutor
+
+    with ThreadPoolExecutor(min(16, os.cpu_count() or 1)) as ex:
+        qs = list(ex.map(lambda i: synth.planted_queries(args.seed, N, D, B, qseed=1000 + i)[0], range(n_batches)))
     q_dev = torch.from_numpy(np.stack(qs)).to(dev)
     q_ready = torch.cuda.Event()  # the queries are resident from here on (lets the search prep them early)
     q_ready.record()
@@ -672,11 +702,14 @@ def main():
                 "post_before_prev_end_us": med(e1[:-1] - post[1:]),
                 "first_start_after_prev_first_end_us": med(s0[1:] - e0[:-1]),
                 "instances_run": int(pst["runs"])}
-    # one untimed batch of isotropic queries (the worst case for ranking: no planted neighbour), for the
+    if args.dump_outputs and rank == 0:  # (every rank holds the same merged answers)
+        dump_outputs(args.dump_outputs, s_dev[-1], r_dev[-1])
+    # --full: one untimed batch of isotropic queries (the worst case for ranking: no planted neighbour), for the
     # recall checks; every rank takes part (the merge is collective)
-    q_iso = isotropic_queries(B, D)
-    s_iso, r_iso = searcher.search(torch.from_numpy(q_iso).to(dev), K)
-    torch.cuda.synchronize()
+    if args.full:
+        q_iso = isotropic_queries(B, D)
+        s_iso, r_iso = searcher.search(torch.from_numpy(q_iso).to(dev), K)
+        torch.cuda.synchronize()
     if G > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -689,8 +722,11 @@ def main():
 
     # Every rank merges the same gathered candidates, so every rank must hold the same answers: a SHA-256 of each
     # rank's timed results (and the isotropic batch) is all-gathered and compared -- the
-    # 8-GPU run proves its own cross-rank agreement instead of checking rank 0 against the oracle alone
-    ranks_agree, digest = results_agree(torch, dist, dev, G, (s_dev[args.warmup:], r_dev[args.warmup:], s_iso, r_iso))
+    # 8-GPU run proves its own cross-rank agreement instead of checking rank 0 against the oracle alone (--full)
+    ranks_agree, digest = True, None
+    if args.full:
+        ranks_agree, digest = results_agree(torch, dist, dev, G,
+                                            (s_dev[args.warmup:], r_dev[args.warmup:], s_iso, r_iso))
 
     qps = args.steps * B / elapsed
     ms_per_step = 1000.0 * elapsed / args.steps
@@ -729,7 +765,7 @@ def main():
                    "exchange": (f"all-gather of the candidate records: {searcher.transport}" if searcher.collective
                                 else "none (one shard: local copy)")},
         # the ranks' merged answers (timed batches + the isotropic batch) hash identically on every rank
-        "ranks_agree": ranks_agree, "result_sha256": digest,
+        **({"ranks_agree": ranks_agree, "result_sha256": digest} if args.full else {}),
         "rccl_ranks": searcher.rccl.G if searcher.rccl is not None else None,
         "roofline": {"bound": "hbm",
                      "kernel": ("k_filter_q256 (256-query FILTER: one pass for four 64-query groups)" if q256 else
@@ -793,14 +829,14 @@ def main():
                 result["roofline"]["profiled_busy_ms_per_launch"] = round(prof["k_scan_filter_busy_ms_per_launch"], 4)
 
     # recall@10 against the oracle's exact answer over the full corpus (rank 0)
-    if rank == 0 and not args.no_cpu:
+    if rank == 0 and args.full and not args.no_cpu:
         nq = min(args.recall_queries, B)
         result.update(recall_checks(args, N, D, K, qs[args.warmup][:nq], r_dev[args.warmup, :nq].cpu().numpy(),
                                     s_dev[args.warmup, :nq].cpu().numpy(), q_iso[:nq],
                                     r_iso[:nq].cpu().numpy(), s_iso[:nq].cpu().numpy()))
 
     # the reference's embed + search query path on the GPU (N = 1), beside cpu_baseline's CPU embed + search
-    if rank == 0 and G == 1 and not args.no_cpu and not args.no_embed:
+    if rank == 0 and G == 1 and args.full and not args.no_cpu and not args.no_embed:
         try:
             result["gpu_embed_plus_search"] = gpu_embed_plus_search(args, searcher, dev, D, K, B)
         except Exception as e:  # report, never hide
@@ -809,7 +845,7 @@ def main():
     # CPU baselines, rank 0, N=1 only: the reference's search path on the host cores (cpu_baseline),
     # the reference's per-query loop and the CPU query embedding beside it, and the exact fp64 oracle
     # (the checker, cpu_oracle) -- each on a bounded sample, scaled to the full corpus
-    if rank == 0 and G == 1 and not args.no_cpu:
+    if rank == 0 and G == 1 and args.full and not args.no_cpu:
         try:
             result["cpu_baseline"] = cpu_reference_baseline(args, qs[args.warmup:], N, D, K, B)
         except Exception as e:  # report, never hide

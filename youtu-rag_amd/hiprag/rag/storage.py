@@ -31,7 +31,7 @@ reference stores (faiss_store.py:98; Chroma float32), so rankings and scores are
 ``dtype: bf16`` (opt-in) halves the bytes per row and doubles the scan rate; search is then exact
 over the stored bf16 values, whose ranking departs from the fp32 answer where two rows' scores lie
 within the bf16 rounding of their dot products: recall@10 against the exact fp32 top-10 measured
-0.99 at 1M-10M rows (bench.py ``recall_at_10_vs_fp32``, tests/test_gpu_scale.py).  Chroma returns the raw fp32
+0.99 at 1M-10M rows (bench.py --full ``recall_at_10_vs_fp32``, tests/test_gpu_scale.py).  Chroma returns the raw fp32
 embedding it stored (chroma_store.py:233-244): ``keep_embeddings: true`` keeps a host fp32
 copy for ``get_by_id`` / ``include_embeddings``; without it they return the stored
 (normalised, quantised) row.
