@@ -279,6 +279,41 @@ int hr_index_stats(hr_index* h, int64_t out[3]);
  * batches to two 128-query FILTER launches instead (A/B; hr_index_q256_launches in include/hiprag_diag.h counts
  * its launches). */
 int hr_index_set_q256(hr_index* h, int on);
+
+/* Keyword (BM25) search: the lexical index behind HybridRetriever (the reference's HybridRetriever only delegates
+ * to the vector retriever and names the debt, base_retriever.py:123-139: "a full hybrid retrieval would include
+ * keyword-based search (e.g., BM25) and combine scores").  A forward index -- per row its distinct 22-bit term ids
+ * ascending, packed `term << 10 | tf` (tf = min(count, 1023)), and dl = min(token count, 65535) -- in CSR arrays on
+ * ONE device, scanned once per query batch.  Scores are the BM25 sum in 64-bit fixed point (2^-32 units, every
+ * term contribution computed in fp64 without contraction and rounded half-to-even), so they do not depend on the
+ * summation order and equal a CPU restatement bit for bit (DESIGN.md "Keyword search").  Statistics (N, df, avgdl)
+ * are over live rows; a row mask does not change them.  Row numbers are append positions, as hr_index's. */
+typedef struct hr_lex hr_lex;
+#define HR_LEX_TERM_BITS 22    /* term id = crc32(token) % 2^22 */
+#define HR_LEX_MAX_QTERMS 64   /* distinct terms of one query (the smallest ids are kept) */
+#define HR_LEX_MAX_K 1024      /* largest top-k (hr_topk_records' limit) */
+/* Host only (no GPU): pack the raw token ids (each < 2^22) of n texts -- text i = tokens[offsets[i] ..
+ * offsets[i+1]) -- into entries_out (capacity entries_cap; the token count always suffices), row_off_out[n + 1]
+ * (CSR offsets from 0) and dl_out[n]. */
+int hr_lex_pack(const uint32_t* tokens, const int64_t* offsets, int64_t n, uint32_t* entries_out, int64_t entries_cap,
+                int64_t* row_off_out, uint16_t* dl_out);
+int hr_lex_create(int device, hr_lex** out);
+void hr_lex_destroy(hr_lex* h);
+/* Append n rows (hr_lex_pack of the tokens); the device arrays grow by doubling. */
+int hr_lex_add(hr_lex* h, const uint32_t* tokens, const int64_t* offsets, int64_t n, int64_t* first_row_out);
+/* Tombstone rows and take them out of N, df and sum_dl; removing a dead row is a no-op. */
+int hr_lex_remove(hr_lex* h, const int64_t* rows, int64_t n);
+int hr_lex_size(hr_lex* h, int64_t* n_out, int64_t* n_live_out);
+/* The global statistics: N (live rows) and the sum of dl over them; df of n_terms given term ids. */
+int hr_lex_stats(hr_lex* h, int64_t* n_live_out, int64_t* sum_dl_out);
+int hr_lex_df(hr_lex* h, const uint32_t* terms, int64_t n_terms, int32_t* df_out);
+/* Top-k of B queries -- query i = term ids q_terms[q_off[i] .. q_off[i+1]) (de-duplicated, capped at
+ * HR_LEX_MAX_QTERMS, terms no live row holds ignored) -- among the live rows the mask allows (row_mask: host
+ * bitmap as hr_index_search's, nullable) that hold at least one of its terms.  1 <= k <= HR_LEX_MAX_K, any B.
+ * Out: B*k fp64 scores and rows, (score desc, row asc), -inf / -1 past the hits. */
+int hr_lex_search(hr_lex* h, const uint32_t* q_terms, const int64_t* q_off, int B, int k, double k1, double b,
+                  const uint64_t* row_mask, double* scores_out, int64_t* rows_out);
+
 const char* hr_last_error(void);
 int hr_abi_version(void);
 

@@ -55,6 +55,11 @@ int hr_index_q256_launches(hr_index* h, int64_t* out);
  * per batch of the busiest shard thread (us), out[2] = batches submitted. */
 int hr_index_host_us(hr_index* h, double* out);
 
+/* Diagnostics: device time of the most recent hr_lex_search by HIP events, summed over its sub-batches --
+ * out[0] = the forward-index scan (k_lex_score and the segment padding), out[1] = the top-k selection (ms),
+ * out[2] = sub-batches.  Zeros when the call launched nothing (no query had a known term). */
+int hr_lex_last_ms(hr_lex* h, double* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,9 @@ DTYPES = {"f32": 0, "float32": 0, "fp32": 0, "bf16": 1, "bfloat16": 1, "f16": 2,
 METRICS = {"cosine": 0, "ip": 1, "dot": 1, "euclidean": 2, "l2": 2}
 HR_MAX_K = 128   # include/hiprag.h
 HR_MAX_KC = 256
+HR_LEX_TERM_BITS = 22    # term id = crc32(token) % 2**22
+HR_LEX_MAX_QTERMS = 64
+HR_LEX_MAX_K = 1024
 
 
 def kc_for_k(k: int, dim: int = 0) -> int:
@@ -49,6 +52,8 @@ EXPORTS = [
     "hr_index_persist_stats", "hr_index_persist_trace", "hr_index_wave_tiles", "hr_index_set_cu_mask",
     "hr_stream_create_cu_mask", "hr_stream_destroy", "hr_index_set_q256", "hr_index_q256_launches",
     "hr_index_search_shard_exact", "hr_merge_sorted", "hr_memcpy_async", "hr_attn_varlen", "hr_gelu_erf",
+    "hr_lex_pack", "hr_lex_create", "hr_lex_destroy", "hr_lex_add", "hr_lex_remove", "hr_lex_size", "hr_lex_stats",
+    "hr_lex_df", "hr_lex_search", "hr_lex_last_ms",
 ]
 
 _lib = None
@@ -174,6 +179,15 @@ def load_library(path: str | None = None):
             "hr_index_graph_replays": [vp, vp],
             "hr_index_wide_launches": [vp, vp],
             "hr_add_layernorm": [vp, vp, vp, vp, vp, i64, i32, ctypes.c_float, i32, vp],
+            "hr_lex_pack": [vp, vp, i64, vp, i64, vp, vp],
+            "hr_lex_create": [i32, pp],
+            "hr_lex_add": [vp, vp, vp, i64, vp],
+            "hr_lex_remove": [vp, vp, i64],
+            "hr_lex_size": [vp, vp, vp],
+            "hr_lex_stats": [vp, vp, vp],
+            "hr_lex_df": [vp, vp, i64, vp],
+            "hr_lex_search": [vp, vp, vp, i32, i32, ctypes.c_double, ctypes.c_double, vp, vp, vp],
+            "hr_lex_last_ms": [vp, vp],
         }
         for name, args in sig.items():
             if p != (path or LIB_PATH) and not hasattr(L, name):
@@ -183,6 +197,9 @@ def load_library(path: str | None = None):
             fn.restype = i32
         L.hr_index_destroy.argtypes = [vp]
         L.hr_index_destroy.restype = None
+        if hasattr(L, "hr_lex_destroy"):
+            L.hr_lex_destroy.argtypes = [vp]
+            L.hr_lex_destroy.restype = None
         L.hr_last_error.argtypes = []
         L.hr_last_error.restype = ctypes.c_char_p
         L.hr_abi_version.restype = i32
@@ -532,6 +549,104 @@ class NativeIndex:
             raise ValueError(f"{path}: index is dim={d.value} dtype={dtype_f} metric={metric_f}, "
                              f"not dim={dim} dtype={dtype} metric={metric}")
         return cls(d.value, dtype_f, metric_f, devs[0], devices=devs, _handle=h)
+
+
+def _csr(lists) -> tuple[np.ndarray, np.ndarray]:
+    """uint32 values and int64 offsets of a list of id sequences (or an (ids, offsets) pair, passed through)."""
+    if isinstance(lists, tuple) and len(lists) == 2 and isinstance(lists[1], np.ndarray):
+        return np.ascontiguousarray(lists[0], np.uint32), np.ascontiguousarray(lists[1], np.int64)
+    off = np.zeros(len(lists) + 1, np.int64)
+    for i, t in enumerate(lists):
+        off[i + 1] = off[i] + len(t)
+    vals = np.empty(int(off[-1]), np.uint32)
+    for i, t in enumerate(lists):
+        vals[off[i]:off[i + 1]] = t
+    return vals, off
+
+
+def lex_pack(token_lists) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Host only (hr_lex_pack): the packed rows of raw token-id lists -- (entries `term << 10 | tf` uint32 sorted by
+    term within a row, CSR offsets int64, dl uint16)."""
+    tok, off = _csr(token_lists)
+    n = len(off) - 1
+    ent = np.empty(max(len(tok), 1), np.uint32)
+    row_off = np.zeros(n + 1, np.int64)
+    dl = np.zeros(n, np.uint16)
+    _check(load_library().hr_lex_pack(_ptr(tok), _ptr(off), n, _ptr(ent), len(tok), _ptr(row_off), _ptr(dl)))
+    return ent[: int(row_off[-1])].copy(), row_off, dl
+
+
+class NativeLexIndex:
+    """The lexical (BM25) forward index on one device (an hr_lex handle); rows are append positions."""
+
+    def __init__(self, device: int = 0):
+        self.lib = load_library()
+        self.device = int(device)
+        h = ctypes.c_void_p()
+        _check(self.lib.hr_lex_create(self.device, ctypes.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.lib.hr_lex_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add(self, token_lists) -> int:
+        """Append one row per token-id list (ids < 2**22); returns the first new row."""
+        tok, off = _csr(token_lists)
+        first = ctypes.c_int64(0)
+        _check(self.lib.hr_lex_add(self._h, _ptr(tok), _ptr(off), len(off) - 1, ctypes.byref(first)))
+        return first.value
+
+    def remove(self, rows) -> None:
+        r = np.ascontiguousarray(np.asarray(rows, np.int64).reshape(-1))
+        _check(self.lib.hr_lex_remove(self._h, _ptr(r), len(r)))
+
+    def size(self) -> tuple[int, int]:
+        n, live = ctypes.c_int64(0), ctypes.c_int64(0)
+        _check(self.lib.hr_lex_size(self._h, ctypes.byref(n), ctypes.byref(live)))
+        return n.value, live.value
+
+    def stats(self) -> tuple[int, int]:
+        """(N, sum_dl) over the live rows."""
+        n, s = ctypes.c_int64(0), ctypes.c_int64(0)
+        _check(self.lib.hr_lex_stats(self._h, ctypes.byref(n), ctypes.byref(s)))
+        return n.value, s.value
+
+    def df(self, terms) -> np.ndarray:
+        t = np.ascontiguousarray(np.asarray(terms, np.uint32).reshape(-1))
+        out = np.zeros(len(t), np.int32)
+        _check(self.lib.hr_lex_df(self._h, _ptr(t), len(t), _ptr(out)))
+        return out
+
+    def search(self, query_terms, k: int, mask: np.ndarray | None = None, k1: float = 1.2, b: float = 0.75
+               ) -> tuple[np.ndarray, np.ndarray]:
+        """(scores float64 (B, k), rows int64 (B, k)) of one term-id list per query; -inf / -1 past the hits."""
+        qt, qo = _csr(query_terms)
+        B = len(qo) - 1
+        s = np.empty((B, k), np.float64)
+        r = np.empty((B, k), np.int64)
+        m = None
+        if mask is not None:
+            m = np.ascontiguousarray(mask, np.uint64).reshape(-1)
+            n_rows = self.size()[0]
+            if len(m) * 64 < n_rows:  # the library reads one bit per row
+                raise ValueError(f"row mask has {len(m)} words, the index {n_rows} rows (needs {(n_rows + 63) // 64})")
+        _check(self.lib.hr_lex_search(self._h, _ptr(qt), _ptr(qo), B, int(k), float(k1), float(b), _ptr(m), _ptr(s),
+                                      _ptr(r)))
+        return s, r
+
+    def last_ms(self) -> tuple[float, float, int]:
+        """Device time of the most recent search: (scan ms, top-k ms, sub-batches) (hr_lex_last_ms)."""
+        out = (ctypes.c_double * 3)()
+        _check(self.lib.hr_lex_last_ms(self._h, out))
+        return out[0], out[1], int(out[2])
 
 
 def gen_rows_device(seed: int, row0: int, n: int, dim: int, out_ptr: int, stream: int = 0) -> None:

@@ -311,16 +311,88 @@ class BatchedVectorRetriever(VectorRetriever):
         return [await self._finish(q, r, top_k) for q, r in zip(queries, results)]
 
 
-class HybridRetriever(BaseRetriever):
-    """Delegates to VectorRetriever, as the reference does (base_retriever.py:102-154)."""
+def rrf_fuse(dense: list, lexical: list, rrf_k: float = 60.0) -> list[tuple]:
+    """Reciprocal-rank fusion of two rankings given as (key, rank, payload) lists (ranks from 1): per key
+    ``sum over the lists holding it of 1 / (rrf_k + rank)``, the dense term added first; returns (key, fused score,
+    payload) by fused score descending, then key ascending (the payload of the first list that holds the key)."""
+    fused: dict = {}
+    for hits in (dense, lexical):
+        for key, rank, payload in hits:
+            term = 1.0 / (rrf_k + rank)
+            if key in fused:
+                fused[key][0] += term
+            else:
+                fused[key] = [term, payload]
+    return [(key, v[0], v[1]) for key, v in sorted(fused.items(), key=lambda kv: (-kv[1][0], kv[0]))]
 
-    def __init__(self, vector_store: BaseVectorStore, embedder: BaseEmbedder, config: RetrieverConfig | None = None):
-        self.vector_retriever = BatchedVectorRetriever(vector_store=vector_store, embedder=embedder, config=config)
+
+class HybridRetriever(BaseRetriever):
+    """Dense + keyword retrieval fused by reciprocal rank (the reference's HybridRetriever delegates to the vector
+    retriever and leaves the rest as a TODO, base_retriever.py:102-154: "a full hybrid retrieval would include
+    keyword-based search (e.g., BM25) and combine scores").
+
+    Over a store with a lexical index (HipVectorStore with ``index_params.lexical``: it has ``keyword_search_batch``)
+    every query runs the dense search and the BM25 keyword search at depth ``fetch_k`` (default
+    ``min(128, max(4 * top_k, 50))``) and the two rankings are fused: ``fused(chunk) = sum of 1 / (rrf_k + rank)`` over
+    the lists that hold it (ranks from 1, the dense term added first), ordered by fused score descending, then chunk
+    row ascending.  ``similarity_threshold`` drops dense hits as in VectorRetriever (ranks taken before it); keyword
+    hits are not thresholded.  Then the optional reranker and ``[:top_k]``.  Over any other store: the delegation."""
+
+    def __init__(self, vector_store: BaseVectorStore, embedder: BaseEmbedder, config: RetrieverConfig | None = None,
+                 reranker: BaseReranker | None = None, *, fusion: str = "rrf", rrf_k: float = 60,
+                 fetch_k: int | None = None):
+        if fusion != "rrf":
+            raise ValueError(f"unsupported fusion {fusion!r} (only 'rrf')")
+        self.vector_retriever = BatchedVectorRetriever(vector_store=vector_store, embedder=embedder, config=config,
+                                                       reranker=reranker)
+        self.vector_store, self.embedder = vector_store, embedder
         self.config = config or RetrieverConfig()
+        self.fusion, self.rrf_k, self.fetch_k = fusion, float(rrf_k), fetch_k
+
+    @property
+    def reranker(self):
+        return self.vector_retriever.reranker
+
+    def _keyword_search(self):
+        fn = getattr(self.vector_store, "keyword_search_batch", None)
+        return fn if callable(fn) and getattr(self.vector_store, "lexical", True) else None
+
+    def _row_of(self, chunk) -> tuple:
+        """The fusion key of a chunk: its row in the store (unknown stores: the order of its id)."""
+        row_of = getattr(self.vector_store, "row_of", None)
+        row = row_of(chunk.id) if row_of is not None else None
+        return (0, row, "") if row is not None else (1, 0, chunk.id)
 
     async def retrieve(self, query: str, top_k: int | None = None, **kwargs) -> list[RetrievalResult]:
-        return await self.vector_retriever.retrieve(query=query, top_k=top_k, **kwargs)
+        if self._keyword_search() is None:
+            return await self.vector_retriever.retrieve(query=query, top_k=top_k, **kwargs)
+        return (await self.batch_retrieve([query], top_k=top_k, **kwargs))[0]
 
     async def batch_retrieve(self, queries: list[str], top_k: int | None = None, **kwargs
                              ) -> list[list[RetrievalResult]]:
-        return await self.vector_retriever.batch_retrieve(queries=queries, top_k=top_k, **kwargs)
+        keyword_search = self._keyword_search()
+        if keyword_search is None:
+            return await self.vector_retriever.batch_retrieve(queries=queries, top_k=top_k, **kwargs)
+        if not queries:
+            return []
+        top_k = top_k or self.config.top_k
+        threshold = kwargs.get("similarity_threshold", self.config.similarity_threshold)
+        filters = kwargs.get("filters")
+        fetch_k = self.fetch_k or min(128, max(4 * top_k, 50))
+        vr = self.vector_retriever
+        embed_many = getattr(self.embedder, "embed_queries", None)
+        qvs = await embed_many(queries) if embed_many else [await self.embedder.embed_query(q) for q in queries]
+        search_batch = getattr(self.vector_store, "search_batch", None)
+        if search_batch is not None:
+            dense = search_batch(qvs, fetch_k, filters)
+        else:
+            dense = [await self.vector_store.search(query_embedding=qv, top_k=fetch_k, filters=filters) for qv in qvs]
+        lexical = keyword_search(queries, fetch_k, filters)
+        out = []
+        for q, d_hits, l_hits in zip(queries, dense, lexical):
+            d = [(self._row_of(r.chunk), r.rank, r.chunk) for r in vr._to_results(d_hits, threshold)]
+            lx = [(self._row_of(c), pos + 1, c) for pos, (c, _) in enumerate(l_hits)]
+            fused = rrf_fuse(d, lx, self.rrf_k)
+            results = [RetrievalResult(chunk=c, score=s, rank=i + 1) for i, (_, s, c) in enumerate(fused)]
+            out.append(await vr._finish(q, results, top_k))
+        return out

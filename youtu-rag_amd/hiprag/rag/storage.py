@@ -39,6 +39,11 @@ copy for ``get_by_id`` / ``include_embeddings``; without it they return the stor
 Persistence: generation snapshots + an append-only journal (persist.py); ``add_chunks`` and
 ``delete*`` write O(chunk) bytes.  ``index_params.devices`` (list of GPU ids) shards the rows
 of one collection over several GPUs inside one handle (hr_index_create with n_dev > 1).
+
+Keyword search (opt-in, ``index_params.lexical: true``; single device): a BM25 forward index (lexical.py) holds the
+chunk contents row for row beside the dense index -- every add, delete and clear goes to both, a load rebuilds it
+from the stored contents (no file of its own) -- and ``keyword_search`` / ``keyword_search_batch`` answer through the
+same tables and the same ``filters`` bitmaps as ``search_batch``.  HybridRetriever fuses the two rankings.
 """
 from __future__ import annotations
 
@@ -58,6 +63,7 @@ from .. import _native
 from . import filters as F
 from . import persist as P
 from .base import BaseVectorStore, Chunk
+from .lexical import MAX_K as _LEX_MAX_K, LexicalIndex
 from .config import VectorStoreConfig
 
 try:  # the per-hit result assembly in C (csrc/host/hostfast.c, built by csrc/Makefile); host-side only, same output
@@ -329,13 +335,18 @@ def _filter_key(filters) -> str:
 
 
 class HipVectorStore(BaseVectorStore):
-    def __init__(self, config: VectorStoreConfig, *, index_factory=None, index_loader=None):
+    def __init__(self, config: VectorStoreConfig, *, index_factory=None, index_loader=None, lexical_factory=None):
         self.config = config
         params = dict(config.index_params or {})
+        self.lexical = bool(params.get("lexical", False))
         self.dtype = params.get("dtype", "f32")  # the reference's store dtype; bf16 is an opt-in
         devs = params.get("devices")
         self.devices = [int(d) for d in devs] if devs else [int(params.get("device", 0))]
         self.device = self.devices[0]
+        if self.lexical and len(self.devices) > 1:
+            raise ValueError("index_params.lexical needs a single-device store (the lexical index is not sharded)")
+        self._lex_factory = lexical_factory or (lambda: LexicalIndex(
+            self.device, float(params.get("bm25_k1", 1.2)), float(params.get("bm25_b", 0.75))))
         self.capacity = int(params.get("capacity", 0))
         self.include_embeddings = bool(params.get("include_embeddings", False))
         self.keep_embeddings = bool(params.get("keep_embeddings", False))
@@ -369,6 +380,9 @@ class HipVectorStore(BaseVectorStore):
         # tables must not resolve its rows through the new ones
         self._epoch = getattr(self, "_epoch", 0) + 1
         self._index = None
+        if getattr(self, "_lex", None) is not None:
+            self._lex.close()
+        self._lex = None  # the lexical index (index_params.lexical), created with the first rows
         self.dim: int | None = None
         # host tables, one entry per index row (None = deleted): a tuple of atoms (id, document_id, content,
         # chunk_index) and the stored metadata dict.  Kept apart on purpose: a tuple of atoms and a dict of
@@ -452,6 +466,7 @@ class HipVectorStore(BaseVectorStore):
                 self._id_to_row[rec[0]] = row
                 self._doc_rows.setdefault(rec[1], array("q")).append(row)
         self._cols.append([m or {} for m in self._metas])
+        self._lex_append(0, [None if t is None else t[2] for t in self._records])
         if self.keep_embeddings:
             self._raw = np.zeros((max(len(records), 1024), self.dim), np.float32)
             if raw is not None and len(raw) == len(records):
@@ -553,6 +568,7 @@ class HipVectorStore(BaseVectorStore):
                 self._id_to_row[rec["id"]] = first + i
                 self._doc_rows.setdefault(rec["document_id"], array("q")).append(first + i)
         self._cols.append([(rec or {}).get("metadata", {}) for rec in records])
+        self._lex_append(first, [None if rec is None else rec["content"] for rec in records])
         n = len(self._records)
         if len(self._live) < n:
             live = np.zeros(max(n, 2 * len(self._live), 1024), bool)
@@ -567,6 +583,19 @@ class HipVectorStore(BaseVectorStore):
                 self._raw = raw
             if vectors is not None:
                 self._raw[first:n] = vectors
+
+    def _lex_append(self, first: int, contents: list):
+        """The same rows into the lexical index (None: a dead row -- it takes its row number and no terms)."""
+        if not self.lexical or not contents:
+            return
+        if self._lex is None:
+            self._lex = self._lex_factory()
+        got = self._lex.add_texts([c or "" for c in contents])
+        if got != first:
+            raise RuntimeError(f"lexical index row {got} != host table row {first}")
+        dead = [first + i for i, c in enumerate(contents) if c is None]
+        if dead:
+            self._lex.remove_rows(dead)
 
     def _register(self, fresh: list[Chunk], first: int, vectors: np.ndarray | None):
         records = [self._record(c) for c in fresh]
@@ -632,6 +661,8 @@ class HipVectorStore(BaseVectorStore):
         if not rows:
             return 0
         self._index.remove(np.asarray(rows, np.int64))
+        if self._lex is not None:
+            self._lex.remove_rows(rows)
         for r in rows:
             rec = self._records[r]
             self._id_to_row.pop(rec[0], None)
@@ -714,6 +745,9 @@ class HipVectorStore(BaseVectorStore):
             if self._index is not None:
                 self._index.close()
                 self._index = None
+            if self._lex is not None:
+                self._lex.close()
+                self._lex = None
 
     # ---------------------------------------------------------------- reads
     def _chunk(self, row: int, embedding=None, tables=None) -> Chunk:
@@ -740,6 +774,30 @@ class HipVectorStore(BaseVectorStore):
         """Batched search: one GPU launch for all queries (BatchedVectorRetriever, the micro-batcher)."""
         prep = self._prep_search(query_embeddings, top_k, filters)
         return self._assemble(prep, self._run_search(prep))
+
+    def keyword_search_batch(self, queries: list[str], top_k: int = 5, filters: dict[str, Any] | None = None
+                             ) -> list[list[tuple[Chunk, float]]]:
+        """BM25 keyword search of the chunk contents (``index_params.lexical``): per query its (Chunk, score) list,
+        score descending then row ascending, among the rows ``filters`` allows that hold at least one of the query's
+        terms.  One forward-index scan on the GPU for the whole batch; same tables, lock and filter bitmaps as
+        search_batch."""
+        if not self.lexical:
+            raise ValueError("keyword search needs index_params.lexical = true")
+        queries = list(queries)
+        with self._lock:
+            tables = (self._records, self._metas, self._epoch)
+            n_live = self.count_sync()
+            if self._lex is None or n_live == 0 or int(top_k) <= 0 or not queries:
+                return [[] for _ in queries]
+            k = min(int(top_k), n_live)
+            if k > _LEX_MAX_K:
+                raise ValueError(f"keyword search returns at most {_LEX_MAX_K} hits per query")
+            raw = self._lex.search(queries, k, self.filter_bitmap(filters))
+        return self._assemble((queries, int(top_k), filters), (raw, tables))
+
+    def keyword_search(self, query: str, top_k: int = 5, filters: dict[str, Any] | None = None
+                       ) -> list[tuple[Chunk, float]]:
+        return self.keyword_search_batch([query], top_k, filters)[0]
 
     # search_batch in three steps, so the micro-batcher can run only the middle one in a worker thread
     # (it holds the GIL for little but the ctypes call; a worker doing the Python parts was starved by
@@ -912,6 +970,10 @@ class HipVectorStore(BaseVectorStore):
 
     async def get_by_id(self, chunk_id: str) -> Chunk | None:
         return await asyncio.to_thread(self.get_by_id_sync, chunk_id)
+
+    def row_of(self, chunk_id: str) -> int | None:
+        """The index row of a stored chunk (None: not stored) -- the tie-break order of fused rankings."""
+        return self._id_to_row.get(chunk_id)
 
     def count_sync(self) -> int:
         return len(self._id_to_row)
