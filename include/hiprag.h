@@ -238,7 +238,12 @@ int hr_add_layernorm(const void* x_dev, const void* r_dev, const void* gamma_dev
  * with fp32 accumulation, the softmax in fp32, P rounded to the input type for the P V product (as the flash
  * kernel), the output rounded once.  BertSelfAttention (modeling_bert.py) on the real tokens, as
  * scaled_dot_product_attention per sequence.  HR_E_UNSUPPORTED outside its scope (d != 64, max_len > 64, fp32,
- * rows not 16-byte aligned): the caller's flash varlen kernel serves those. */
+ * rows not 16-byte aligned): the caller's flash varlen kernel serves those.
+ * PRECONDITION: max_len >= cu[b+1] - cu[b] for every b, and cu is non-decreasing.  max_len is the only thing that
+ * decides whether the kernel applies; the kernel reads the lengths on the device and never compares them with it, so
+ * with an understated max_len the rows of a sequence longer than 64 tokens are undefined (its first 64 rows are
+ * computed from tiles indexed past their 64 keys, the rest are never written) and no error is reported.  Empty
+ * sequences (cu[b+1] == cu[b]) are allowed and write nothing; only the N = cu[B] rows of out_dev are written. */
 int hr_attn_varlen(const void* qkv_dev, int dtype, const int32_t* cu_dev, int B, int nH, int d, int max_len,
                    float scale, void* out_dev, void* stream);
 /* In place: x = 0.5 x (1 + erf(x / sqrt 2)) (BertIntermediate's "gelu", torch.nn.functional.gelu with

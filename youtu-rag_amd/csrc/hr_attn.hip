@@ -4,12 +4,15 @@
 // A 64-query batch at the bge-large shape is ~1,900 tokens in ~64 sequences of ~30 tokens.  Per layer torch's
 // variable-length flash attention took 19 us plus a 5 us fill of its own (profiles/r06_embed_forward_kernels.json),
 // for work that is ~110 MFLOP and ~15 MB of traffic: its tiles are sized for long sequences.  Here:
-//  * k_attn_short: one workgroup per (sequence, head), the sequence's K and V rows staged in LDS as fp32, one
-//    thread per query row with its scaled q row and the output accumulator in registers, an online softmax over
-//    the keys (running max, rescaled sum) -- the function of scaled_dot_product_attention on each sequence (every
-//    token attends to its own sequence only, no mask inside it), fp32 throughout from the bf16 / f16 projections,
-//    the output rounded once (RNE).  Sequences up to kMaxL tokens (query and short-passage batches); longer ones
-//    are the flash kernel's (hr_attn_varlen returns HR_E_UNSUPPORTED and the caller takes that path).
+//  * k_attn_mfma: one workgroup of two waves per (head, sequence), wave w the query rows [32 w, 32 w + 32).  The
+//    raw scores S^T = K Q^T per 32-key tile on v_mfma_f32_32x32x16 straight from the projections' rows (fp32
+//    accumulation), a two-pass softmax in fp32 (the row maximum, then p = exp((s - max) * scale) and the row sum
+//    of the unrounded p; a lane holds one query's 16 keys of a tile, its partner lane ^ 32 the other 16), P rounded
+//    to the input type into LDS, O^T = V^T P^T on MFMA against V^T staged in LDS, times 1 / row sum, rounded once
+//    -- the function of scaled_dot_product_attention on each sequence (every token attends to its own sequence
+//    only, no mask inside it).  Sequences up to kMaxL tokens (query and short-passage batches); longer ones are
+//    the flash kernel's (hr_attn_varlen returns HR_E_UNSUPPORTED and the caller takes that path).  The caller's
+//    max_len must bound every length in cu (include/hiprag.h): the kernel does not check it.
 //  * k_gelu_erf: BertIntermediate's exact (erf) GELU in place, 0.5 x (1 + erf(x / sqrt 2)) in fp32 per element,
 //    rounded once -- torch's GeluCUDAKernelImpl's formula and opmath; 16-byte vectors, a grid sized to the tensor.
 #include <hip/hip_runtime.h>

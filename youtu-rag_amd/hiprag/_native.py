@@ -773,6 +773,8 @@ def add_layernorm(x, r, weight, bias, eps: float):
     x, r = x.contiguous(), r.contiguous()
     out = torch.empty_like(x)
     H = x.shape[-1]
+    if x.numel() == 0:  # no rows (an empty tensor's pointer is null, which the C entry rejects)
+        return out
     _check(load_library().hr_add_layernorm(ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(r.data_ptr()),
                                            ctypes.c_void_p(weight.data_ptr()), ctypes.c_void_p(bias.data_ptr()),
                                            ctypes.c_void_p(out.data_ptr()), x.numel() // H, H, float(eps),
