@@ -259,6 +259,14 @@ int hr_gelu_erf(void* x_dev, int dtype, int64_t n, void* stream);
  * counters and stamps: hr_index_persist_stats / _trace, include/hiprag_diag.h.) */
 int hr_index_set_persist(hr_index* h, int mode);
 int hr_index_persist_close(hr_index* h);
+/* The 8-bit shadow of a cosine corpus (any stored dtype): an int8 copy of the rows with one fp32 scale per row, kept
+ * beside them (+50 % of a 16-bit corpus' memory; built lazily after row writes, never written to files;
+ * HIPRAG_SHADOW8=0 at create, or a failed allocation, keeps none; HIPRAG_SHADOW8_SIM_OOM=1 makes that allocation
+ * fail whenever the rows grow -- for tests of the fallback).  The SAMPLE and the 64-query FILTER of a main pass
+ * stream it instead of the 16-bit rows; candidates are rescored from the stored rows and the exactness guard carries
+ * the shadow's measured error, so results are unchanged.  set_shadow8: 0 off, 1 (default) shards beyond 5.1M rows --
+ * where it measured faster, 2 wherever the path is built (one query group, k up to 32, a single-device index). */
+int hr_index_set_shadow8(hr_index* h, int mode);
 /* CU partitioning (no reference counterpart: the reference's embedder and store are separate services, here the
  * query embedder's forward and the scan share one GPU -- base_retriever.py:57-63 embed_query -> search).
  * set_cu_mask: this index's internal streams run on the CUs of `mask` only (bit i of word j = CU 32 j + i;

@@ -38,6 +38,14 @@ int hr_index_last_scan_ms(hr_index* h, float* sample_ms, float* filter_ms);
 /* Diagnostics: approximate MFMA scores of every row (B <= 64; approx_out B×n) and the
  * per-query error bound E_q that the exactness guard uses (e_out, B). */
 int hr_index_debug_approx(hr_index* h, const float* q, int B, float* approx_out, double* e_out);
+/* The same for the shadow-8 scan (hr_index_set_shadow8): its approximate scores (f16 queries, int8 rows, row scale)
+ * and its E_q, which carries u_x8.  HR_E_UNSUPPORTED when the index keeps no 8-bit shadow. */
+int hr_index_debug_approx8(hr_index* h, const float* q, int B, float* approx_out, double* e_out);
+/* Diagnostics of the shadow-8 scan: out[0] = shadow-8 FILTER launches issued so far (graph replays not counted),
+ * out[1] = candidate depth kc8 the most recent one planned (selected and rescored per query before the trim to the
+ * caller's kc), out[2] = 1 if the index keeps an 8-bit shadow; *u_x8 (nullable) = the guard's storage term, the
+ * largest |x - scale * int8| over the stored rows relative to the largest row norm. */
+int hr_index_shadow8_stats(hr_index* h, int64_t out[3], double* u_x8);
 /* Diagnostics: candidates appended by the most recent FILTER scan (sum, max per query). */
 int hr_index_last_candidates(hr_index* h, int64_t* total, int64_t* max_per_query);
 

@@ -7,6 +7,9 @@
 namespace hr {
 
 enum { F32 = 0, BF16 = 1, F16 = 2 };
+// scan-only operand type (never a stored dtype): the 8-bit shadow of a cosine corpus (hr_internal.hpp rows8) --
+// biased int8 (byte = value + 128), one 1 KiB block per PAIR of k-steps, one fp32 scale per row
+enum { I8S = 3 };
 enum { COSINE = 0, IP = 1, L2 = 2 };
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));

@@ -87,11 +87,16 @@ extern "C" int hr_index_create(int dim, int dtype, int metric, int n_dev, const 
         const char* e = std::getenv("HIPRAG_F32_SHADOW");
         h->shadow = dtype == F32 && !(e && e[0] == '0');
         h->shadow_lo = INT64_MAX;
+        const char* e8 = std::getenv("HIPRAG_SHADOW8");  // 0: no 8-bit shadow (also what a failed allocation leaves)
+        h->shadow8 = metric == COSINE && !(e8 && e8[0] == '0');
+        h->shadow8_lo = INT64_MAX;
     }
     hipError_t e = hipSetDevice(dev);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipMalloc(&h->norm_bits, sizeof(unsigned long long));
     if (e == hipSuccess) e = hipMemset(h->norm_bits, 0, sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMalloc(&h->err8_bits, sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemset(h->err8_bits, 0, sizeof(unsigned long long));
     hipDeviceProp_t prop;
     if (e == hipSuccess) e = hipGetDeviceProperties(&prop, dev);
     if (e != hipSuccess) {
@@ -110,8 +115,56 @@ int index_grow(hr_index* h, int64_t need_rows) {
     const size_t tb = tile_bytes(h);
     uint8_t* nr = nullptr;
     uint32_t* nl = nullptr;
-    HIP_TRY(hipMalloc(&nr, (size_t)(new_cap / 32) * tb));
+    auto drop_shadow8 = [&]() {  // the index goes on without an 8-bit shadow (scans stream the 16-bit rows)
+        (void)hipStreamSynchronize(h->stream);
+        if (h->rows8) (void)hipFree(h->rows8);
+        if (h->scale8) (void)hipFree(h->scale8);
+        h->rows8 = nullptr;
+        h->scale8 = nullptr;
+        h->shadow8 = false;
+        h->shadow8_lo = INT64_MAX;
+    };
+    if (hipMalloc(&nr, (size_t)(new_cap / 32) * tb) != hipSuccess) {
+        // no room for the grown rows: give the optional shadow's memory back and try once more (nothing of the
+        // index has been freed or replaced yet, so a second failure leaves it as it was)
+        (void)hipGetLastError();
+        if (!h->rows8) return set_err(HR_E_HIP, "index_grow: out of device memory for the rows");
+        drop_shadow8();
+        HIP_TRY(hipMalloc(&nr, (size_t)(new_cap / 32) * tb));
+    }
     HIP_TRY(hipMemsetAsync(nr, 0, (size_t)(new_cap / 32) * tb, h->stream));
+    if (h->shadow8) {  // the 8-bit shadow grows with the rows (its converted tiles carried over); before anything
+                       // of the old index is freed, and never failing the grow
+        const size_t tb8 = (size_t)h->S * 512;
+        uint8_t* n8 = nullptr;
+        float* ns = nullptr;
+        const bool sim_oom = [] { const char* e = std::getenv("HIPRAG_SHADOW8_SIM_OOM"); return e && e[0] == '1'; }();
+        if (sim_oom || hipMalloc(&n8, (size_t)(new_cap / 32) * tb8) != hipSuccess ||
+            hipMalloc(&ns, (size_t)new_cap * 4) != hipSuccess) {
+            (void)hipGetLastError();
+            if (n8) (void)hipFree(n8);
+            drop_shadow8();
+        } else {
+            hipError_t e8 = hipMemsetAsync(n8, 0x80, (size_t)(new_cap / 32) * tb8, h->stream);  // biased zeros
+            if (e8 == hipSuccess) e8 = hipMemsetAsync(ns, 0, (size_t)new_cap * 4, h->stream);
+            if (e8 == hipSuccess && h->rows8) {
+                e8 = hipMemcpyAsync(n8, h->rows8, (size_t)(h->cap / 32) * tb8, hipMemcpyDeviceToDevice, h->stream);
+                if (e8 == hipSuccess)
+                    e8 = hipMemcpyAsync(ns, h->scale8, (size_t)h->cap * 4, hipMemcpyDeviceToDevice, h->stream);
+            }
+            if (e8 == hipSuccess) e8 = hipStreamSynchronize(h->stream);
+            if (e8 != hipSuccess) {
+                (void)hipFree(n8);
+                (void)hipFree(ns);
+                (void)hipFree(nr);
+                return set_err(HR_E_HIP, std::string("index_grow (8-bit shadow): ") + hipGetErrorString(e8));
+            }
+            if (h->rows8) (void)hipFree(h->rows8);
+            if (h->scale8) (void)hipFree(h->scale8);
+            h->rows8 = n8;
+            h->scale8 = ns;
+        }
+    }
     HIP_TRY(hipMalloc(&nl, (size_t)(new_cap / 32) * 4));
     HIP_TRY(hipMemsetAsync(nl, 0, (size_t)(new_cap / 32) * 4, h->stream));
     float* nx = nullptr;
@@ -633,6 +686,25 @@ static int launch_scan(hr_index* h, Scratch& sc, int cus, const Plan& pl, const 
     });
 }
 
+// the shadow-8 SAMPLE / 64-query FILTER (XFrag<F16, I8S>): f16 queries whatever the stored dtype, a ring of P8
+// 16-byte loads (each a pair of k-steps), P8 the deepest of 16 / 8 / 4 / 2 dividing S / 2.  One query group only.
+template <int MODE>
+static int launch_scan8(hr_index* h, Scratch& sc, int cus, const Plan& pl, const ScanArgs& a, hipStream_t st) {
+    static_assert(MODE == SCAN_SAMPLE || MODE == SCAN_FILTER, "the collect pass reads the 16-bit rows");
+    int lds = scan_lds_bytes(h, pl.QB);
+    if (MODE == SCAN_SAMPLE) lds = std::max(lds, (kScanThreads / 64) * pl.QB * 16 * 64 * 4 + 64);
+    const int S8 = h->S / 2;
+    const int P8 = S8 % 16 == 0 ? 16 : (S8 % 8 == 0 ? 8 : (S8 % 4 == 0 ? 4 : 2));
+    constexpr bool NT = MODE == SCAN_FILTER;  // (the SAMPLE's tiles are the same every batch: default policy, as above)
+    if (MODE == SCAN_FILTER) h->n_shadow8++;
+#define HR_SCAN8_CASE(QBv, Pv) \
+    if (pl.QB == QBv && P8 == Pv) return launch_scan_t<F16, I8S, QBv, Pv, MODE, NT>(h, sc, cus, a, st, lds);
+    HR_SCAN8_CASE(2, 16) HR_SCAN8_CASE(1, 16) HR_SCAN8_CASE(2, 8) HR_SCAN8_CASE(1, 8) HR_SCAN8_CASE(2, 4)
+    HR_SCAN8_CASE(1, 4) HR_SCAN8_CASE(2, 2) HR_SCAN8_CASE(1, 2)
+#undef HR_SCAN8_CASE
+    return set_err(HR_E_INVALID, "no shadow-8 scan variant for this plan");
+}
+
 // CUs left to the tail stream while a pipelined scan runs: the scan reads HBM at the same rate
 // on 224 of the 256 CUs (measured: 6.85 vs 6.81 TB/s at 10M rows, 0.434 vs 0.427 ms at 1.25M),
 // so select/rescore, the RCCL all-gather and the merge of the previous batch run beside it
@@ -800,8 +872,106 @@ __global__ __launch_bounds__(256) void k_shadow(const uint8_t* __restrict__ rows
     *(u32x4*)(rows16 + (t * S + c) * 1024 + lane * 16) = o;
 }
 
-// bring the shadow up to the rows (h->stream, synchronous; never inside a capture: the graph path calls it first)
+// stored rows [r0, r1) -> the 8-bit shadow (hr_index::rows8): one wave per row.  scale = max|x| / 127 (fp32), value =
+// round-to-nearest-even(x / scale) clamped to +-127, stored biased by 128; an all-zero row gets scale 0 and zeros.
+// |x - scale * value| against the STORED row in fp64 (the product scale * value is exact there), raised into
+// err_bits by atomicMax (non-negative doubles order as their bits).  Lane c owns 8-element chunks as in k_store;
+// chunk c = (k-step c / 2, half c % 2) lands in paired block c / 4, bytes 8 * ((c / 2) % 2) of the lane's 16.
+template <int DT>
+__global__ __launch_bounds__(256) void k_shadow8(const uint8_t* __restrict__ rows, uint8_t* __restrict__ rows8,
+                                                 float* __restrict__ scale8, int S, int64_t r0, int64_t r1,
+                                                 unsigned long long* err_bits) {
+    const int lane = threadIdx.x & 63;
+    const int64_t r = r0 + (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= r1) return;  // (wave-uniform)
+    const int nchunk = S * 2;
+    const int sl = row_slot(r);
+    auto chunk = [&](int c, float (&v)[8]) {
+        const int s = c >> 1, hh = c & 1;
+        const int64_t ch = (r >> 5) * S + s;
+        if constexpr (DT == F32) {
+            const float4 a = *(const float4*)(rows + ch * 2048 + (sl + 32 * hh) * 16);
+            const float4 b = *(const float4*)(rows + ch * 2048 + 1024 + (sl + 32 * hh) * 16);
+            v[0] = a.x, v[1] = a.y, v[2] = a.z, v[3] = a.w, v[4] = b.x, v[5] = b.y, v[6] = b.z, v[7] = b.w;
+        } else {
+            const u32x4 w = *(const u32x4*)(rows + ch * 1024 + (sl + 32 * hh) * 16);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const uint16_t hq = (uint16_t)(w[j >> 1] >> (16 * (j & 1)));
+                v[j] = DT == BF16 ? bf16_to_f32(hq) : f16_to_f32(hq);
+            }
+        }
+    };
+    float mx = 0.0f;
+    for (int c = lane; c < nchunk; c += 64) {
+        float v[8];
+        chunk(c, v);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) mx = fmaxf(mx, fabsf(v[j]));
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
+    const float scale = mx / 127.0f;
+    double e2 = 0.0;
+    for (int c = lane; c < nchunk; c += 64) {
+        float v[8];
+        chunk(c, v);
+        uint32_t lo = 0, hi = 0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            float qv = scale > 0.0f ? __builtin_rintf(v[j] / scale) : 0.0f;
+            qv = fminf(127.0f, fmaxf(-127.0f, qv));
+            const double d = (double)v[j] - (double)scale * (double)qv;
+            e2 += d * d;
+            const uint32_t byte = (uint32_t)((int)qv + 128);
+            if (j < 4) lo |= byte << (8 * j);
+            else hi |= byte << (8 * (j - 4));
+        }
+        const int s = c >> 1, hh = c & 1;
+        uint2* dst = (uint2*)(rows8 + ((r >> 5) * (S / 2) + (s >> 1)) * 1024 + (sl + 32 * hh) * 16 + 8 * (s & 1));
+        *dst = make_uint2(lo, hi);
+    }
+    e2 = wave_butterfly_sum(e2);
+    if (lane == 0) {
+        scale8[r] = scale;
+        // (rounded up: the guard takes this as an upper bound)
+        const double e = __builtin_sqrt(e2) * (1.0 + 0x1p-40);
+        atomicMax(err_bits, (unsigned long long)__builtin_bit_cast(uint64_t, e));
+    }
+}
+
+// the shards whose main pass scans the shadow in mode 1: beyond the dual-FILTER and persistent ranges
+static bool shadow8_in_range(const hr_index* h) { return (h->n + 31) / 32 > 160 * 1024; }
+
+// force: convert even where no scan would read the shadow (diagnostics).  Otherwise a shard below mode 1's range
+// leaves its stale tiles for later (shadow8_lo keeps the first of them): no conversion, no wait after every add
+static int shadow8_update(hr_index* h, bool force = false) {
+    if (!h->rows8 || h->shadow8_lo == INT64_MAX) return HR_OK;
+    if (!force && (h->shadow8_mode == 0 || (h->shadow8_mode == 1 && !shadow8_in_range(h)))) return HR_OK;
+    const int64_t r1 = h->n, r0 = std::min(h->shadow8_lo * 32, r1);
+    if (r1 > r0) {
+        if (int rc = set_device(h)) return rc;
+        int rc = dispatch_dt(h->dtype, [&](auto dt) -> int {
+            hipLaunchKernelGGL((k_shadow8<decltype(dt)::value>), dim3((unsigned)((r1 - r0 + 3) / 4)), dim3(256), 0, h->stream,
+                               h->rows, h->rows8, h->scale8, h->S, r0, r1, h->err8_bits);
+            HIP_TRY(hipGetLastError());
+            return HR_OK;
+        });
+        if (rc) return rc;
+        unsigned long long bits = 0;
+        HIP_TRY(hipMemcpyAsync(&bits, h->err8_bits, sizeof(bits), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        double v;
+        std::memcpy(&v, &bits, 8);
+        h->err8 = std::max(h->err8, v);
+    }
+    h->shadow8_lo = INT64_MAX;
+    return HR_OK;
+}
+
+// bring the shadows up to the rows (h->stream, synchronous; never inside a capture: the graph path calls it first)
 int shadow_update(hr_index* h) {
+    if (int rc = shadow8_update(h)) return rc;
     if (!h->rows16 || h->shadow_lo == INT64_MAX) return HR_OK;
     const int64_t t1 = (h->n + 31) / 32, t0 = std::min(h->shadow_lo, t1);
     if (t1 > t0) {
@@ -832,6 +1002,49 @@ static double storage_u(const hr_index* h) {
     return std::ldexp(1.0, -11) + (mn > 0.0 ? std::sqrt((double)h->dpad) * std::ldexp(1.0, -25) / mn : 0.0);
 }
 
+// shadow-8 scans: storage term u_x8 = max_r |x_r - scale_r i_r| / max norm over the stored rows (k_shadow8), and the
+// accumulation term with the fp32 scale multiply's rounding (2^-24, taken as 2^-23) folded in and taken against
+// the shadow's own norm |scale i| <= (1 + u_x8) max norm
+static double storage_u8(const hr_index* h) {
+    const double mn = std::sqrt(h->max_norm2);
+    return mn > 0.0 ? h->err8 / mn * (1.0 + 1e-12) : 0.0;
+}
+static double acc_gamma8(const hr_index* h) { return (acc_gamma(h) + std::ldexp(1.0, -23)) * (1.0 + storage_u8(h)); }
+
+// Candidate depth of a shadow-8 scan for top-k (DESIGN.md "Shadow-8 depth"): the guard's window E_q is ~5x the
+// 16-bit scan's, so the scan selects and rescores kc8 = k + 4 x the 16-bit margin, rounded up to a row part, plus
+// one part, and trims the exact candidates to the caller's kc afterwards (k_trim).  0: deeper than five row parts
+// (kShadow8MaxKc) -- that k keeps the 16-bit scan.  *kj8: the starting floor's rank (as hr_rank_for).
+static int kc_margin(int k, int dim);
+static constexpr int kShadow8MaxKc = 160;  // five row parts, as the k = 100 plan of the 16-bit scan
+static int kc8_for(int k, int kc, int dim, int* kj8) {
+    const int want = k + 4 * kc_margin(k, dim);
+    const int kc8 = std::max((want + 31) / 32 * 32 + 32, (kc + 31) / 32 * 32);
+    if (k <= 0 || kc8 > kShadow8MaxKc) return 0;
+    *kj8 = want + 32 < kc8 ? want + 32 : 0;
+    return kc8;
+}
+
+// exact candidates [B][kci] (k_rescore's) -> the best kc of each query by (score desc, row asc), empty slots last:
+// what a shadow-8 scan hands the caller.  A dropped candidate sorts after kc >= k returned ones of its own shard, so
+// it is in no top-k; the shard bound (over the rows that were never candidates) is unchanged.
+static __global__ __launch_bounds__(256) void k_trim(const Cand* __restrict__ in, int kci, int kc, Cand* __restrict__ out) {
+    const Cand* c = in + (int64_t)blockIdx.x * kci;
+    for (int i = threadIdx.x; i < kci; i += blockDim.x) {
+        const Cand a = c[i];
+        const uint64_t ka = a.row < 0 ? 0 : d2key(a.score);
+        const int64_t ra = a.row < 0 ? INT64_MAX : a.row;
+        int rank = 0;
+        for (int j = 0; j < kci; ++j) {
+            const Cand b = c[j];
+            const uint64_t kb = b.row < 0 ? 0 : d2key(b.score);
+            const int64_t rb = b.row < 0 ? INT64_MAX : b.row;
+            rank += (kb > ka || (kb == ka && (rb < ra || (rb == ra && j < i)))) ? 1 : 0;
+        }
+        if (rank < kc) out[(int64_t)blockIdx.x * kc + rank] = a.row < 0 ? Cand{-__builtin_inf(), -1} : a;
+    }
+}
+
 // One chunk of <= Bp queries on this shard.  mode 0: top-kc via SAMPLE+FILTER(groups);
 // mode 1: collect every row with approx >= floor (exact fallback).
 // st_tail: stream of select + rescore (the outputs are ready in its order).  st_tail != st:
@@ -840,7 +1053,7 @@ static double storage_u(const hr_index* h) {
 static int shard_chunk(hr_index* h, const float* q_dev, int B, int kc, int kj, const uint64_t* mask_dev, int64_t row_offset,
                        const double* kth_dev_host /* mode 1: host array of kth, B */, int mode, int cap_out,
                        Cand* cand_out, double* bound_out, hipStream_t st, hipStream_t st_tail,
-                       hipEvent_t q_ready = nullptr) {
+                       hipEvent_t q_ready = nullptr, int k8 = 0 /* the search's k: > 0 allows a shadow-8 scan */) {
     if (int rc = shadow_update(h)) return rc;
     Plan pl;
     if (int rc = make_plan(h, B, &pl)) return rc;
@@ -886,7 +1099,24 @@ static int shard_chunk(hr_index* h, const float* q_dev, int B, int kc, int kj, c
                        n_tiles >= std::max<int64_t>(early_min_tiles, 8 * sample_target(n_tiles));
     // the persistent FILTER (hr_persist.hip) takes this batch: its FILTER runs in the instance streaming the
     // batches one after another; prep, SAMPLE, select and rescore are this function's as for any pipelined batch
-    const bool persist = mode == 0 && !wide_likely && persist_wanted(h, pl, (kc + 31) / 32, early, mask_dev, n_tiles);
+    // The shadow-8 scan (hr_internal.hpp rows8) takes this batch's SAMPLE and FILTER: a main pass of one query group
+    // on a single-device index, at a k the row parts serve, and (mode 1) on a shard beyond the dual-FILTER and
+    // persistent ranges -- the single-stream FILTER's, where it was measured.  It selects and rescores kc8 >= kc
+    // candidates and trims them to the caller's kc (kc8_for).
+    int kj8 = 0;
+    const int kc8 = (mode == 0 && k8 > 0 && h->rows8 && h->shadow8_lo == INT64_MAX && h->shadow8_mode > 0 &&
+                     h->stripe_G == 1 && pl.NG == 1 && !wide_likely && (h->shadow8_mode == 2 || shadow8_in_range(h)))
+                        ? kc8_for(k8, kc, h->dim, &kj8)
+                        : 0;
+    const bool use8 = kc8 > 0;
+    const int kc_caller = kc;
+    if (use8) {
+        kc = kc8;
+        kj = kj8;
+        h->last_kc8 = kc8;
+    }
+    const bool persist = mode == 0 && !wide_likely && !use8 &&
+                         persist_wanted(h, pl, (kc + 31) / 32, early, mask_dev, n_tiles);
     uint32_t pepoch = 0;
     int pslot = 0;
     if (persist) {
@@ -977,7 +1207,7 @@ static int shard_chunk(hr_index* h, const float* q_dev, int B, int kc, int kj, c
     HIP_TRY(sc.overflow.ensure((size_t)Bp * 4));
     HIP_TRY(sc.dyn_q.ensure((size_t)std::max(4, pl.NG) * 64));
 
-    const int MT = mfma_type(h);
+    const int MT = use8 ? F16 : mfma_type(h);  // (shadow-8: f16 queries whatever the stored dtype)
     float* fl = mode == 0 ? sc.floor_q.as<float>() : nullptr;  // else uploaded below
     if (MT == BF16)
         hipLaunchKernelGGL((k_prep_q<BF16>), dim3((Bp + 3) / 4), dim3(256), 0, sp, q_dev, B, Bp, h->dim, h->dpad,
@@ -1019,7 +1249,8 @@ static int shard_chunk(hr_index* h, const float* q_dev, int B, int kc, int kj, c
     }
 
     ScanArgs a{};
-    a.rows = scan_rows(h);
+    a.rows = use8 ? h->rows8 : scan_rows(h);
+    a.rscale = use8 ? h->scale8 : nullptr;
     a.xnorm = h->metric == L2 ? h->xnorm : nullptr;
     a.live = h->live;
     a.mask = (const uint32_t*)mask_dev;
@@ -1079,7 +1310,9 @@ static int shard_chunk(hr_index* h, const float* q_dev, int B, int kc, int kj, c
             a.sample_stride = std::max<int64_t>(1, n_vis / s_target);
             a.n_units = (n_vis + a.sample_stride - 1) / a.sample_stride;
             if (timed) HIP_TRY(hipEventRecord(ev.e[0], sp));
-            if (int rc = launch_scan(h, sc, early ? spare : cus, pl, a, SCAN_SAMPLE, sp)) return rc;
+            if (int rc = use8 ? launch_scan8<SCAN_SAMPLE>(h, sc, early ? spare : cus, pl, a, sp)
+                              : launch_scan(h, sc, early ? spare : cus, pl, a, SCAN_SAMPLE, sp))
+                return rc;
             // a strided sample: start the thresholds at the kj-th largest sampled group maximum (k_floor_kth; a
             // sample of every tile -- small shards -- leaves the floor)
             if (kj > 0 && a.sample_stride > 1) {
@@ -1148,7 +1381,9 @@ static int shard_chunk(hr_index* h, const float* q_dev, int B, int kc, int kj, c
             h->last_scr = &sc;
         } else {
             if (timed) HIP_TRY(hipEventRecord(ev.e[1], sf));
-            if (int rc = launch_scan(h, sc, cus, pl, a, groups ? SCAN_FILTER : SCAN_COLLECT, sf)) return rc;
+            if (int rc = use8 ? launch_scan8<SCAN_FILTER>(h, sc, cus, pl, a, sf)
+                              : launch_scan(h, sc, cus, pl, a, groups ? SCAN_FILTER : SCAN_COLLECT, sf))
+                return rc;
         }
         if (timed) {
             if (!persist) HIP_TRY(hipEventRecord(ev.e[3], sf));
@@ -1184,16 +1419,25 @@ static int shard_chunk(hr_index* h, const float* q_dev, int B, int kc, int kj, c
     HIP_TRY(hipGetLastError());
     // rescore
     const int64_t nw = (int64_t)B * kc_sel;
+    Cand* resc_out = cand_out;
+    if (use8 && kc != kc_caller) {
+        HIP_TRY(sc.cand8.ensure((size_t)Bp * kc * sizeof(Cand)));
+        resc_out = sc.cand8.as<Cand>();
+    }
     int rc = dispatch_dt(h->dtype, [&](auto dt) -> int {
         hipLaunchKernelGGL((k_rescore<decltype(dt)::value>), dim3((unsigned)((nw + 3) / 4)), dim3(256), 0, st_tail, h->rows,
                            h->S, h->dpad, sc.q32.as<float>(), sc.sel_rows.as<uint32_t>(), sc.sel_cnt.as<int>(), B,
                            kc_sel, row_offset, sc.bound_approx.as<float>(), sc.qerr.as<double>(), max_norm,
-                           acc_gamma(h), storage_u(h), h->metric, sc.overflow.as<int>(), cand_out, bound_out,
-                           h->stripe_G, h->stripe_s);
+                           use8 ? acc_gamma8(h) : acc_gamma(h), use8 ? storage_u8(h) : storage_u(h), h->metric,
+                           sc.overflow.as<int>(), resc_out, bound_out, h->stripe_G, h->stripe_s);
         HIP_TRY(hipGetLastError());
         return HR_OK;
     });
     if (rc) return rc;
+    if (resc_out != cand_out) {
+        hipLaunchKernelGGL(k_trim, dim3(B), dim3(256), 0, st_tail, resc_out, kc, kc_caller, cand_out);
+        HIP_TRY(hipGetLastError());
+    }
     if (piped) {
         HIP_TRY(hipEventRecord(sc.released, st_tail));
         sc.armed = true;
@@ -1228,13 +1472,13 @@ static int shard_chunk(hr_index* h, const float* q_dev, int B, int kc, int kj, c
 
 static int shard_search(hr_index* h, const float* q_dev, int B, int kc, int kj, const uint64_t* mask_dev, int64_t row_offset,
                         Cand* cand_out, double* bound_out, hipStream_t st, hipStream_t st_tail,
-                        hipEvent_t q_ready = nullptr) {
+                        hipEvent_t q_ready = nullptr, int k8 = 0) {
     Plan pl;
     if (int rc = make_plan(h, B, &pl)) return rc;
     for (int b0 = 0; b0 < B; b0 += pl.Bp) {
         const int bc = std::min(pl.Bp, B - b0);
         if (int rc = shard_chunk(h, q_dev + (int64_t)b0 * h->dim, bc, kc, kj, mask_dev, row_offset, nullptr, 0, 0,
-                                 cand_out + (int64_t)b0 * kc, bound_out + b0, st, st_tail, q_ready))
+                                 cand_out + (int64_t)b0 * kc, bound_out + b0, st, st_tail, q_ready, k8))
             return rc;
     }
     return HR_OK;
@@ -1275,7 +1519,7 @@ static int search_main(hr_index* h, const float* q_dev, int B, int k, const uint
     HIP_TRY(h->kth.ensure((size_t)B * 8));
     HIP_TRY(h->fail.ensure((size_t)B * 4));
     if (int rc = shard_search(h, q_dev, B, kc, hr_rank_for(k, kc, h->dim), mask_dev, 0, h->cand.as<Cand>(),
-                              h->bound.as<double>(), st, st))
+                              h->bound.as<double>(), st, st, nullptr, k))
         return rc;
     return launch_merge(h->device, h->cand.as<Cand>(), h->bound.as<double>(), 1, B, kc, k, s_out, r_out,
                         h->kth.as<double>(), h->fail.as<int32_t>(), st);
@@ -1368,7 +1612,8 @@ static int sync_graph_search(hr_index* h, const float* q, int B, int k, float* s
     if (e->disabled) return HR_E_UNSUPPORTED;
     auto current = [&](const hr_index::SyncGraph& g) {
         return g.exec && g.n == h->n && g.rows == h->rows && g.live == h->live && g.xnorm == h->xnorm &&
-               g.max_norm2 == h->max_norm2 && g.pin == h->pin && g.buf_gen == g_buf_gen.load();
+               g.max_norm2 == h->max_norm2 && g.pin == h->pin && g.buf_gen == g_buf_gen.load() &&
+               g.rows8 == h->rows8 && g.err8 == h->err8;  // (the shadow-8 guard term is a captured argument)
     };
     if (!current(*e)) {
         if (e->exec) {  // stale: recapture right away after a buffer moved; after the rows changed
@@ -1430,6 +1675,8 @@ static int sync_graph_search(hr_index* h, const float* q, int B, int k, float* s
         e->live = h->live;
         e->xnorm = h->xnorm;
         e->max_norm2 = h->max_norm2;
+        e->rows8 = h->rows8;
+        e->err8 = h->err8;
         e->pin = h->pin;
         e->buf_gen = gen0;
     }
@@ -1854,7 +2101,7 @@ extern "C" int hr_index_search_shard(hr_index* h, const float* q_dev, int B, int
     if (kc < k || kc > HR_MAX_KC) return set_err(HR_E_INVALID, "kc must be in [k, HR_MAX_KC]");
     hipStream_t st = (hipStream_t)stream;  // NULL = the null stream (torch's default)
     return shard_search(h, q_dev, B, kc, hr_rank_for(k, kc, h->dim), row_mask_dev, row_offset, (Cand*)cand_out_dev,
-                        bound_out_dev, st, st);
+                        bound_out_dev, st, st, nullptr, k);
 }
 
 extern "C" int hr_index_search_shard_async_ev(hr_index* h, const float* q_dev, int B, int k, int kc,
@@ -1869,7 +2116,7 @@ extern "C" int hr_index_search_shard_async_ev(hr_index* h, const float* q_dev, i
     if (int rc = validate_search(h, B, k)) return rc;
     if (kc < k || kc > HR_MAX_KC) return set_err(HR_E_INVALID, "kc must be in [k, HR_MAX_KC]");
     return shard_search(h, q_dev, B, kc, hr_rank_for(k, kc, h->dim), row_mask_dev, row_offset, (Cand*)cand_out_dev,
-                        bound_out_dev, (hipStream_t)scan_stream, (hipStream_t)tail_stream, (hipEvent_t)q_ready_event);
+                        bound_out_dev, (hipStream_t)scan_stream, (hipStream_t)tail_stream, (hipEvent_t)q_ready_event, k);
 }
 
 extern "C" int hr_index_search_shard_async(hr_index* h, const float* q_dev, int B, int k, int kc,
@@ -1955,11 +2202,23 @@ extern "C" int hr_merge_candidates_strided(int device, const void* cand_dev, con
 
 
 // diagnostics: approximate scores of every row (Bp×n) and the per-query bound E_q
+static int debug_approx_impl(hr_index* h, const float* q, int B, float* approx_out, double* e_out, bool s8);
 extern "C" int hr_index_debug_approx(hr_index* h, const float* q, int B, float* approx_out, double* e_out) {
+    return debug_approx_impl(h, q, B, approx_out, e_out, false);
+}
+// the same for the shadow-8 scan: its approximate scores (f16 queries, int8 rows, row scale) and its E_q
+extern "C" int hr_index_debug_approx8(hr_index* h, const float* q, int B, float* approx_out, double* e_out) {
+    return debug_approx_impl(h, q, B, approx_out, e_out, true);
+}
+static int debug_approx_impl(hr_index* h, const float* q, int B, float* approx_out, double* e_out, bool s8) {
     if (!h || !q || !approx_out || !e_out || B <= 0 || B > 64) return set_err(HR_E_INVALID, "bad arguments");
     std::lock_guard<std::mutex> lk(h->mu);
     if (h->G > 1) return set_err(HR_E_UNSUPPORTED, "diagnostics need a single-device index");
     if (int rc = set_device(h)) return rc;
+    if (s8) {
+        if (!h->rows8) return set_err(HR_E_UNSUPPORTED, "the index keeps no 8-bit shadow");
+        if (int rc = shadow8_update(h, true)) return rc;
+    }
     Plan pl;
     if (int rc = make_plan(h, B, &pl)) return rc;
     hipStream_t st = h->stream;
@@ -1972,7 +2231,7 @@ extern "C" int hr_index_debug_approx(hr_index* h, const float* q, int B, float* 
     HIP_TRY(sc.qerr.ensure((size_t)Bp * 4 * 8));
     HIP_TRY(h->stage.ensure((size_t)Bp * n_tiles * 32 * 4 + 16));
     HIP_TRY(hipMemcpyAsync(h->q_in.p, q, (size_t)B * h->dim * 4, hipMemcpyHostToDevice, st));
-    const int MT = mfma_type(h);
+    const int MT = s8 ? F16 : mfma_type(h);
     if (MT == BF16)
         hipLaunchKernelGGL((k_prep_q<BF16>), dim3((Bp + 3) / 4), dim3(256), 0, st, h->q_in.as<float>(), B, Bp, h->dim,
                            h->dpad, h->S, pl.QB, h->metric, sc.q32.as<float>(), sc.qfrag.as<uint16_t>(), sc.qerr.as<double>(),
@@ -1983,7 +2242,14 @@ extern "C" int hr_index_debug_approx(hr_index* h, const float* q, int B, float* 
                            nullptr, 1, nullptr, nullptr, nullptr);
     HIP_TRY(hipGetLastError());
     const int lds = scan_lds_bytes(h, pl.QB);
-    int rc = dispatch_dt(h->dtype, [&](auto dt) -> int {
+    int rc = s8 ? [&]() -> int {
+        auto kern = pl.QB == 1 ? k_debug_approx<F16, I8S, 1> : k_debug_approx<F16, I8S, 2>;
+        HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        hipLaunchKernelGGL(kern, dim3((unsigned)((n_tiles + 3) / 4)), dim3(256), lds, st, h->rows8,
+                           sc.qfrag.as<uint16_t>(), h->S, n_tiles, nullptr, h->stage.as<float>(), h->scale8);
+        HIP_TRY(hipGetLastError());
+        return HR_OK;
+    }() : dispatch_dt(h->dtype, [&](auto dt) -> int {
         constexpr int DT = decltype(dt)::value;
         constexpr int MTc = DT == F16 ? F16 : BF16;
         auto k1 = k_debug_approx<MTc, DT, 1>;
@@ -1995,7 +2261,7 @@ extern "C" int hr_index_debug_approx(hr_index* h, const float* q, int B, float* 
         HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         hipLaunchKernelGGL(kern, dim3((unsigned)((n_tiles + 3) / 4)), dim3(256), lds, st, h->rows,
                            sc.qfrag.as<uint16_t>(), h->S, n_tiles, h->metric == L2 ? h->xnorm : nullptr,
-                           h->stage.as<float>());
+                           h->stage.as<float>(), (const float*)nullptr);
         HIP_TRY(hipGetLastError());
         return HR_OK;
     });
@@ -2008,7 +2274,8 @@ extern "C" int hr_index_debug_approx(hr_index* h, const float* q, int B, float* 
     const double max_norm = std::sqrt(h->max_norm2) * (1.0 + 1e-12);
     for (int b = 0; b < B; ++b) {
         std::memcpy(approx_out + (size_t)b * h->n, tmp.data() + (size_t)b * n_tiles * 32, (size_t)h->n * 4);
-        e_out[b] = guard_e(&qerr[4 * (size_t)b], max_norm, acc_gamma(h), storage_u(h), h->metric);
+        e_out[b] = guard_e(&qerr[4 * (size_t)b], max_norm, s8 ? acc_gamma8(h) : acc_gamma(h),
+                           s8 ? storage_u8(h) : storage_u(h), h->metric);
     }
     return HR_OK;
 }
@@ -2164,6 +2431,9 @@ extern "C" void hr_index_destroy(hr_index* h) {
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     if (h->rows) (void)hipFree(h->rows);
     if (h->rows16) (void)hipFree(h->rows16);
+    if (h->rows8) (void)hipFree(h->rows8);
+    if (h->scale8) (void)hipFree(h->scale8);
+    if (h->err8_bits) (void)hipFree(h->err8_bits);
     if (h->live) (void)hipFree(h->live);
     if (h->xnorm) (void)hipFree(h->xnorm);
     if (h->norm_bits) (void)hipFree(h->norm_bits);
@@ -2469,6 +2739,30 @@ extern "C" int hr_index_q256_launches(hr_index* h, int64_t* out) {
     int64_t n = h->n_q256;
     for (hr_index* s : h->shards) n += s->n_q256;
     *out = n;
+    return HR_OK;
+}
+
+// shadow-8 scan scope: 0 off, 1 (default) where it measured faster, 2 wherever it is built (tests)
+extern "C" int hr_index_set_shadow8(hr_index* h, int mode) {
+    if (!h || mode < 0 || mode > 2) return set_err(HR_E_INVALID, "mode must be 0, 1 or 2");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (h->shadow8_mode != mode) {
+        if (int rc = set_device(h)) return rc;
+        drop_sync_graphs(h);  // a captured search replays the scan it was captured with
+    }
+    h->shadow8_mode = mode;
+    return HR_OK;
+}
+
+// diagnostics: out[0] shadow-8 FILTER launches issued (not graph replays), out[1] the candidate depth kc8 the most
+// recent one planned, out[2] 1 if the index keeps an 8-bit shadow; *u_x8 (nullable) the guard's storage term
+extern "C" int hr_index_shadow8_stats(hr_index* h, int64_t out[3], double* u_x8) {
+    if (!h || !out) return set_err(HR_E_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    out[0] = h->n_shadow8;
+    out[1] = h->last_kc8;
+    out[2] = h->rows8 ? 1 : 0;
+    if (u_x8) *u_x8 = storage_u8(h);
     return HR_OK;
 }
 

@@ -106,7 +106,8 @@ static constexpr int kScanThreads = 512;
 struct Scratch {
     DevBuf q32, qfrag, qerr, mkeys, floor_q, cnt, buf, sel_rows, sel_cnt, bound_approx, overflow, pbuf, pcnt, dyn_q,
         tl, tl_tmp,  // device-mask tile list (+ its count after the list) and its rocPRIM scratch
-        wtiles;      // diagnostics: tiles each wave of the most recent FILTER launch scanned (ScanArgs::wave_tiles)
+        wtiles,      // diagnostics: tiles each wave of the most recent FILTER launch scanned (ScanArgs::wave_tiles)
+        cand8;       // shadow-8 scan: the exact candidates of its deeper kc, before the trim to the caller's kc
     int64_t last_W = 0, last_Bp = 0;  // waves (per query group) and queries per group of the most recent FILTER
     int last_ng = 1;                  // query groups of that launch
     int last_capw = kCapW;            // candidate slots per (region, query) of that launch
@@ -118,7 +119,7 @@ struct Scratch {
     bool armed = false;               // `released` has been recorded at least once
     void release_all() {
         for (DevBuf* b : {&q32, &qfrag, &qerr, &mkeys, &floor_q, &cnt, &buf, &sel_rows, &sel_cnt, &bound_approx,
-                          &overflow, &pbuf, &pcnt, &dyn_q, &tl, &tl_tmp, &wtiles})
+                          &overflow, &pbuf, &pcnt, &dyn_q, &tl, &tl_tmp, &wtiles, &cand8})
             b->release();
         if (scanned) (void)hipEventDestroy(scanned);
         if (released) (void)hipEventDestroy(released);
@@ -143,6 +144,23 @@ struct hr_index {
     uint8_t* rows16 = nullptr;
     bool shadow = false;
     int64_t shadow_lo = 0;
+    // cosine corpora (any stored dtype): an 8-bit copy of the rows -- biased int8 (byte = round(x / scale) + 128,
+    // |value| <= 127), one 1 KiB block per pair of k-steps (XFrag<F16, I8S>), slot swizzle and tile order as the
+    // rows -- with one fp32 scale = max|x| / 127 per row (scale8[row]), built from the STORED rows.  The SAMPLE and
+    // the 64-query FILTER of the main pass stream it instead of the 16-bit rows (half the bytes); the guard's
+    // storage term is then u_x8 = err8 / max norm, err8 = max_r |x_r - scale_r i_r| over the stored rows (fp64,
+    // device word err8_bits).  Maintained lazily like the 16-bit shadow (shadow8_lo: first stale tile); never
+    // written to files.  shadow8: the corpus keeps one (cosine, allocation succeeded, HIPRAG_SHADOW8 != 0);
+    // shadow8_mode (hr_index_set_shadow8): 0 never scanned, 1 where it measured faster, 2 wherever it is built.
+    uint8_t* rows8 = nullptr;
+    float* scale8 = nullptr;
+    unsigned long long* err8_bits = nullptr;
+    bool shadow8 = false;
+    int shadow8_mode = 1;
+    int64_t shadow8_lo = 0;
+    double err8 = 0.0;
+    int64_t n_shadow8 = 0;          // shadow-8 FILTER launches issued (diagnostics)
+    int last_kc8 = 0;               // candidate depth the most recent shadow-8 scan planned (diagnostics)
     uint32_t* live = nullptr;       // one word per tile
     float* xnorm = nullptr;         // euclidean only: fp32 |x|^2 per stored row (approximate scan score)
     std::vector<uint32_t> live_host;
@@ -193,6 +211,8 @@ struct hr_index {
         const void* rows = nullptr;
         const void* live = nullptr;
         const void* xnorm = nullptr;
+        const void* rows8 = nullptr;
+        double err8 = 0.0;
         const void* pin = nullptr;
         double max_norm2 = 0.0;
         uint64_t buf_gen = 0;
@@ -341,6 +361,7 @@ inline const uint8_t* scan_rows(const hr_index* h) { return h->rows16 ? h->rows1
 // a row writer touched tiles from t0 on (INT64_MAX: the shadow is current)
 inline void shadow_stale(hr_index* h, int64_t t0) {
     if (h->shadow && t0 < h->shadow_lo) h->shadow_lo = t0 < 0 ? 0 : t0;
+    if (h->shadow8 && t0 < h->shadow8_lo) h->shadow8_lo = t0 < 0 ? 0 : t0;
 }
 int shadow_update(hr_index* h);
 

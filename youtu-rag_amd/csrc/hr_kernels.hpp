@@ -287,6 +287,9 @@ struct ScanArgs {
     int teams;
     int dyn_pct;             // dynamic-tail percentage the host used (teams recompute their split)
     int stagger;             // FILTER: refreshes staggered over a workgroup's waves (see roff in scan_body)
+    // 8-bit shadow scans (DT == I8S): fp32 scale per row, [tile * 32 + row % 32]; the accumulators are multiplied
+    // by the lane's row scale before the threshold compare, the group maxima and the append
+    const float* rscale;
 };
 
 
@@ -375,25 +378,28 @@ __device__ inline u32x4 corpus_load(const uint8_t* p) {
 }
 template <int MT, bool NT>
 struct XFrag<MT, BF16, NT> {
-    static constexpr int kLoads = 1;  // 16-byte loads per lane per k-step
+    static constexpr int kLoads = 1;  // 16-byte loads per lane per ring entry
+    static constexpr int kSteps = 1;  // k-steps (MFMAs per query block) a ring entry feeds
     u32x4 v;
     __device__ inline void load(const uint8_t* rows, int64_t c, int lane) {
         v = corpus_load<NT>(rows + c * 1024 + lane * 16);
     }
-    __device__ inline u32x4 get() const { return v; }
+    __device__ inline u32x4 get(int = 0) const { return v; }
 };
 template <int MT, bool NT>
 struct XFrag<MT, F16, NT> {
     static constexpr int kLoads = 1;
+    static constexpr int kSteps = 1;
     u32x4 v;
     __device__ inline void load(const uint8_t* rows, int64_t c, int lane) {
         v = corpus_load<NT>(rows + c * 1024 + lane * 16);
     }
-    __device__ inline u32x4 get() const { return v; }
+    __device__ inline u32x4 get(int = 0) const { return v; }
 };
 template <int MT, bool NT>
 struct XFrag<MT, F32, NT> {
     static constexpr int kLoads = 2;
+    static constexpr int kSteps = 1;
     u32x4 a, b;
     __device__ inline void load(const uint8_t* rows, int64_t c, int lane) {
         a = corpus_load<NT>(rows + c * 2048 + lane * 16);
@@ -403,7 +409,7 @@ struct XFrag<MT, F32, NT> {
     // error-bounded approximate score depends on it (the exact rescoring reads fp32).
     // Whole-vector bit casts: hipcc (ROCm 7.2) mis-lowers __builtin_bit_cast of single
     // ext-vector elements here (it re-used one lane value for all eight).
-    __device__ inline u32x4 get() const {
+    __device__ inline u32x4 get(int = 0) const {
         typedef float f32x4 __attribute__((ext_vector_type(4)));
         typedef float f32x8 __attribute__((ext_vector_type(8)));
         const f32x4 fa = __builtin_bit_cast(f32x4, a);
@@ -414,6 +420,35 @@ struct XFrag<MT, F32, NT> {
         } else {
             return __builtin_bit_cast(u32x4, __builtin_convertvector(f, f16x8));
         }
+    }
+};
+
+// 8-bit shadow: one 16-byte load = the lane's 8 + 8 elements of two consecutive k-steps (bytes 0-7: k-step 2c,
+// bytes 8-15: k-step 2c + 1), each byte the int8 value + 128.  f16 operand by the magic-number form: v_perm_b32
+// puts each byte under 0x64 (the f16 1024 + byte, exact: f16 steps by 1 in [1024, 2048)), one packed f16 subtract of
+// 1152 gives the int8 value, exact -- 4 VALU ops per 4 elements, no per-element cvt.  f16 MFMA only.
+template <bool NT>
+struct XFrag<F16, I8S, NT> {
+    static constexpr int kLoads = 1;
+    static constexpr int kSteps = 2;
+    u32x4 v;
+    __device__ inline void load(const uint8_t* rows, int64_t c, int lane) {
+        v = corpus_load<NT>(rows + c * 1024 + lane * 16);
+    }
+    __device__ inline u32x4 get(int ks) const {
+        typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+        const uint32_t w0 = ks ? v[2] : v[0], w1 = ks ? v[3] : v[1];
+        const f16x2 off = {(_Float16)1152.0f, (_Float16)1152.0f};
+        auto cv = [&](uint32_t w, uint32_t sel) -> uint32_t {
+            const uint32_t m = __builtin_amdgcn_perm(0x64646464u, w, sel);  // bytes 4-7: 0x64, bytes 0-3: w
+            return __builtin_bit_cast(uint32_t, __builtin_bit_cast(f16x2, m) - off);
+        };
+        u32x4 o;
+        o[0] = cv(w0, 0x04010400u);
+        o[1] = cv(w0, 0x04030402u);
+        o[2] = cv(w1, 0x04010400u);
+        o[3] = cv(w1, 0x04030402u);
+        return o;
     }
 };
 
@@ -548,7 +583,9 @@ __device__ __forceinline__ void scan_body(ScanArgs a) {
     const int64_t u0 = strided ? 0 : wr * base + (wr < rem ? wr : rem);
     const int64_t u1 = strided ? (wr < n_static ? (n_static - 1 - wr) / W + 1 : 0) : u0 + base + (wr < rem ? 1 : 0);
     const int64_t stride = FILTER ? 1 : a.sample_stride;
-    const int S = a.S;
+    // ring entries per tile: a k-step each, or (8-bit shadow) a pair of k-steps
+    constexpr int KS = XFrag<MT, DT, NT>::kSteps;
+    const int S = a.S / KS;
     // the plan picks P dividing S (make_plan): every k-loop runs at least once, so its ring waits retire
     // whatever was issued before it (the early refresh loads) -- without this the compiler keeps the
     // zero-trip path and waits for the ring again where those loads are used
@@ -755,7 +792,8 @@ __device__ __forceinline__ void scan_body(ScanArgs a) {
     };
     uint32_t rkey[QB][16];  // group-max keys of the refresh due in the current tile's epilogue
     // (LEAN: never -- the 32 keys held across the k-loop cost the registers the persistent loop needs)
-    const bool early_refresh = !LEAN && a.early_refresh != 0;
+    // (nor for the 8-bit shadow, whose two converted fragments per ring entry take the registers)
+    const bool early_refresh = !LEAN && DT != I8S && a.early_refresh != 0;
     int64_t u = u0, u_end = u1, pend = -1, done = 0;
     // a.stagger: refreshes staggered over the workgroup's waves (wave v refreshes after tiles with (done + v) % RT
     // == 0) -- each tile some waves publish and read fresh keys instead of all of them every RT-th tile.  Large
@@ -815,21 +853,32 @@ __device__ __forceinline__ void scan_body(ScanArgs a) {
         // the whole ring: vmcnt(0) at every tile)
         uint32_t allow = scalar_word(a.live, t);
         if (a.mask) allow &= scalar_word(a.mask, t);
+        // 8-bit shadow: this lane's row scale, issued like a refresh's loads before the k-loop (older than every
+        // ring load the loop issues, so the loop's own ring waits retire it) and used in the epilogue
+        float rsc = 1.0f;
+        if constexpr (DT == I8S) {
+            rsc = a.rscale[t * 32 + rg];
+            asm volatile("" ::: "memory");
+        }
         for (int sb = 0; sb < S; sb += P) {
             const bool same = sb + P < S;
             const int64_t nc = same ? t * S + sb + P : tn * S;
 #pragma unroll
             for (int i = 0; i < P; ++i) {
-                const u32x4 xf = ring[i].get();
+                u32x4 xf[KS];
+#pragma unroll
+                for (int ks = 0; ks < KS; ++ks) xf[ks] = ring[i].get(ks);
                 ring[i].load(a.rows, nc + i, lane);
 #pragma unroll
-                for (int qb = 0; qb < QB; ++qb) {
-                    const u32x4 qf = qs[((sb + i) * QB + qb) * 64 + lane];
-                    if (HR_DIAG & 16)
-                        acc[qb][i & 15] += __builtin_bit_cast(float, (qf.x ^ xf.x) & 0x3f000000u);
-                    else
-                        acc[qb] = mfma32<MT>(qf, xf, acc[qb]);
-                }
+                for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+                    for (int qb = 0; qb < QB; ++qb) {
+                        const u32x4 qf = qs[(((sb + i) * KS + ks) * QB + qb) * 64 + lane];
+                        if (HR_DIAG & 16)
+                            acc[qb][i & 15] += __builtin_bit_cast(float, (qf.x ^ xf[ks].x) & 0x3f000000u);
+                        else
+                            acc[qb] = mfma32<MT>(qf, xf[ks], acc[qb]);
+                    }
             }
         }
 
@@ -865,6 +914,12 @@ __device__ __forceinline__ void scan_body(ScanArgs a) {
             for (int qb = 0; qb < QB; ++qb)
 #pragma unroll
                 for (int i = 0; i < 16; ++i) acc[qb][i] = __builtin_fmaf(xmul, acc[qb][i], -xs);
+        }
+        if constexpr (DT == I8S) {
+#pragma unroll
+            for (int qb = 0; qb < QB; ++qb)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) acc[qb][i] *= rsc;
         }
         const bool ok = (allow >> rg) & 1u;
         const uint32_t row = (uint32_t)(t * 32 + rg);
@@ -1018,7 +1073,8 @@ constexpr auto scan_kernel() {
 template <int MT, int DT, int QB>
 __global__ __launch_bounds__(256) void k_debug_approx(const uint8_t* __restrict__ rows, const uint16_t* __restrict__ qfrag,
                                                       int S, int64_t n_tiles, const float* __restrict__ xnorm,
-                                                      float* __restrict__ out) {
+                                                      float* __restrict__ out,
+                                                      const float* __restrict__ rscale = nullptr) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     stage_lds((u32x4*)lds, (const u32x4*)qfrag, S * QB * 64);
     __syncthreads();
@@ -1031,15 +1087,27 @@ __global__ __launch_bounds__(256) void k_debug_approx(const uint8_t* __restrict_
     for (int qb = 0; qb < QB; ++qb)
 #pragma unroll
         for (int i = 0; i < 16; ++i) acc[qb][i] = 0.0f;
-    for (int s = 0; s < S; ++s) {
+    constexpr int KS = XFrag<MT, DT>::kSteps;
+    for (int s = 0; s < S / KS; ++s) {
         XFrag<MT, DT> x;
-        x.load(rows, t * S + s, lane);
-        const u32x4 xf = x.get();
+        x.load(rows, t * (S / KS) + s, lane);
 #pragma unroll
-        for (int qb = 0; qb < QB; ++qb) acc[qb] = mfma32<MT>(qs[(s * QB + qb) * 64 + lane], xf, acc[qb]);
+        for (int ks = 0; ks < KS; ++ks) {
+            const u32x4 xf = x.get(ks);
+#pragma unroll
+            for (int qb = 0; qb < QB; ++qb)
+                acc[qb] = mfma32<MT>(qs[((s * KS + ks) * QB + qb) * 64 + lane], xf, acc[qb]);
+        }
     }
     const int64_t ncol = n_tiles * 32;
     const int rg = slot_row(t, lane & 31);
+    if (rscale) {  // 8-bit shadow: the same product as k_scan's epilogue
+        const float rsc = rscale[t * 32 + rg];
+#pragma unroll
+        for (int qb = 0; qb < QB; ++qb)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[qb][i] *= rsc;
+    }
     const float xs = xnorm ? xnorm[t * 32 + rg] : 0.0f;  // euclidean: same score as k_scan
 #pragma unroll
     for (int qb = 0; qb < QB; ++qb)

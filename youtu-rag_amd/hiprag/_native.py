@@ -53,7 +53,8 @@ EXPORTS = [
     "hr_stream_create_cu_mask", "hr_stream_destroy", "hr_index_set_q256", "hr_index_q256_launches",
     "hr_index_search_shard_exact", "hr_merge_sorted", "hr_memcpy_async", "hr_attn_varlen", "hr_gelu_erf",
     "hr_lex_pack", "hr_lex_create", "hr_lex_destroy", "hr_lex_add", "hr_lex_remove", "hr_lex_size", "hr_lex_stats",
-    "hr_lex_df", "hr_lex_search", "hr_lex_last_ms",
+    "hr_lex_df", "hr_lex_search", "hr_lex_last_ms", "hr_index_set_shadow8", "hr_index_debug_approx8",
+    "hr_index_shadow8_stats",
 ]
 
 _lib = None
@@ -138,6 +139,9 @@ def load_library(path: str | None = None):
             "hr_index_search_poll": [vp, i64, vp],
             "hr_index_set_persist": [vp, i32],
             "hr_index_persist_close": [vp],
+            "hr_index_set_shadow8": [vp, i32],
+            "hr_index_debug_approx8": [vp, vp, i32, vp, vp],
+            "hr_index_shadow8_stats": [vp, vp, vp],
             "hr_index_persist_stats": [vp, vp],
             "hr_index_persist_trace": [vp, ctypes.c_int, vp, vp],
             "hr_index_wave_tiles": [vp, vp, i32, vp],
@@ -440,6 +444,26 @@ class NativeIndex:
         e = np.empty(q.shape[0], np.float64)
         _check(self.lib.hr_index_debug_approx(self._h, _ptr(q), q.shape[0], _ptr(out), _ptr(e)))
         return out, e
+
+    def debug_approx8(self, q: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
+        """debug_approx for the shadow-8 scan: (its approximate scores B×n, its error bound E per query)."""
+        q = np.ascontiguousarray(q, np.float32)
+        n, _ = self.size()
+        out = np.empty((q.shape[0], n), np.float32)
+        e = np.empty(q.shape[0], np.float64)
+        _check(self.lib.hr_index_debug_approx8(self._h, _ptr(q), q.shape[0], _ptr(out), _ptr(e)))
+        return out, e
+
+    def set_shadow8(self, mode: int) -> None:
+        """Shadow-8 scan of cosine corpora: 0 off, 1 shards beyond 5.1M rows (default), 2 wherever it is built."""
+        _check(self.lib.hr_index_set_shadow8(self._h, int(mode)))
+
+    def shadow8_stats(self) -> dict:
+        """{"launches": shadow-8 FILTER launches, "kc8": depth the last one planned, "built": bool, "u_x8": float}."""
+        out = (ctypes.c_int64 * 3)()
+        u = ctypes.c_double(0.0)
+        _check(self.lib.hr_index_shadow8_stats(self._h, out, ctypes.byref(u)))
+        return {"launches": int(out[0]), "kc8": int(out[1]), "built": bool(out[2]), "u_x8": float(u.value)}
 
     def last_candidates(self) -> tuple[int, int]:
         t, m = ctypes.c_int64(0), ctypes.c_int64(0)
