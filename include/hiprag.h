@@ -68,6 +68,13 @@ enum {
 #define HR_MAX_KC 256          /* largest per-shard candidate count kc (k = HR_MAX_K with its margin) */
 
 int hr_index_create(int dim, int dtype, int metric, int n_dev, const int* dev_ids, hr_index** out);
+/* hr_index_create / hr_index_load with creation flags (single-device handles only; 0 = the plain call).
+ * HR_CREATE_NO_SHADOWS: the index keeps neither the 16-bit shadow of fp32 rows nor the 8-bit shadow of a cosine
+ * corpus -- for an index that never runs a main scan pass, such as the list-order rows behind hr_ivf_search,
+ * whose shadows would only cost memory (+50 % of a 16-bit corpus). */
+enum { HR_CREATE_NO_SHADOWS = 1 };
+int hr_index_create_ex(int dim, int dtype, int metric, int n_dev, const int* dev_ids, int flags, hr_index** out);
+int hr_index_load_ex(const char* path, int n_dev, const int* dev_ids, int flags, hr_index** out);
 int hr_index_reserve(hr_index* h, int64_t capacity_rows);
 int hr_index_add(hr_index* h, const float* rows, int64_t n, int64_t* first_row_out);
 int hr_index_add_synthetic(hr_index* h, uint64_t seed, int64_t global_row0, int64_t n, int64_t* first_row_out);
@@ -81,6 +88,16 @@ int hr_index_add_device(hr_index* h, const float* rows_dev, int64_t n, int64_t* 
  * never written stay dead.  Ordered after the work queued on `stream`; returns once stored. */
 int hr_index_add_device_at(hr_index* h, const float* rows_dev, int64_t n, const int64_t* dest_dev,
                            int64_t n_rows_after, void* stream);
+/* Copy the STORED bits of n rows of src (row numbers src_rows_dev[i]) to the previously unused positions
+ * dst_pos_dev[i] (< n_rows_after) of dst, tile layout to tile layout (the slot swizzle is honoured on both sides);
+ * the positions become live, dst takes src's max norm and then holds n_rows_after rows, as after
+ * hr_index_add_device_at.  Re-adding a stored cosine row through hr_index_add_device_at would normalise it a second
+ * time and could change its bits; this keeps them, so IVF lists hold exactly what the exact index holds.  Pairs
+ * with an index out of range on either side are skipped.  Two different single-device handles on one device with
+ * the same dim, dtype and metric, cosine or dot; anything else: HR_E_UNSUPPORTED.  Ordered after the work queued
+ * on `stream`; returns once copied. */
+int hr_index_copy_rows(hr_index* dst, hr_index* src, const int64_t* src_rows_dev, const int64_t* dst_pos_dev,
+                       int64_t n, int64_t n_rows_after, void* stream);
 /* The synthetic corpus generator (the one hr_index_add_synthetic and the oracle use) writing n fp32
  * rows of dimension dim, row-major, to device memory on `stream`. */
 int hr_gen_rows_device(uint64_t seed, int64_t row0, int64_t n, int dim, float* out_dev, void* stream);
@@ -201,6 +218,22 @@ int hr_ivf_search(hr_index* h, const float* centroids_dev, int nlist, const int6
                   int64_t max_list_tiles, const int64_t* ids_dev, const float* q_dev, int B, int nprobe, int k,
                   const uint64_t* row_mask_dev, void* cand_out_dev, double* bound_out_dev, void* probes_out_dev,
                   void* stream);
+/* hr_ivf_search over growable lists: list l is the sequence of extents ext_dev[e] = {first tile, tile count}
+ * (int64 pairs), e in [ext_off_dev[l], ext_off_dev[l+1]), list_ntiles_dev[l] tiles in all; max_list_tiles is the
+ * largest of those totals.  A list without extents and an extent without tiles are legal.  Same stages and the
+ * same results as hr_ivf_search (only the unit list is built from the extent table); the order of a list's
+ * extents cannot change them, the final selection orders by (score desc, id asc).  The caller keeps the three
+ * tables consistent and every extent inside the index; a tile beyond the index's rows is never read. */
+int hr_ivf_search_ext(hr_index* h, const float* centroids_dev, int nlist, const int64_t* ext_off_dev,
+                      const int64_t* ext_dev, const int64_t* list_ntiles_dev, int64_t max_list_tiles,
+                      const int64_t* ids_dev, const float* q_dev, int B, int nprobe, int k,
+                      const uint64_t* row_mask_dev, void* cand_out_dev, double* bound_out_dev, void* probes_out_dev,
+                      void* stream);
+/* The position-order row mask hr_ivf_search takes (one uint32 word per 32-row tile), from a bitmap by id
+ * (row_mask_dev: uint64 words, n_mask_rows bits): bit p % 32 of out_dev[p / 32] is set iff 0 <= ids_dev[p] <
+ * n_mask_rows and the bitmap has bit ids_dev[p].  Writes ceil(n_positions / 32) words; any n_positions. */
+int hr_ivf_position_mask(const int64_t* ids_dev, int64_t n_positions, const uint64_t* row_mask_dev,
+                         int64_t n_mask_rows, uint32_t* out_dev, void* stream);
 
 /* Exact top-m of B segments of {double score; int64 id} records, order (score desc, id asc), records
  * with id < 0 absent; segment b = [seg_off_records_dev[b], seg_off_records_dev[b+1]) if given, else

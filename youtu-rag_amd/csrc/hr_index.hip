@@ -62,8 +62,15 @@ hipError_t index_stream_create(const hr_index* h, hipStream_t* s, bool high_prio
 
 // ---------------------------------------------------------------- create / grow
 extern "C" int hr_index_create(int dim, int dtype, int metric, int n_dev, const int* dev_ids, hr_index** out) {
+    return hr_index_create_ex(dim, dtype, metric, n_dev, dev_ids, 0, out);
+}
+
+extern "C" int hr_index_create_ex(int dim, int dtype, int metric, int n_dev, const int* dev_ids, int flags,
+                                  hr_index** out) {
     if (!out) return set_err(HR_E_INVALID, "out is null");
     *out = nullptr;
+    if (flags & ~HR_CREATE_NO_SHADOWS) return set_err(HR_E_INVALID, "unknown creation flags");
+    if (flags && n_dev > 1) return set_err(HR_E_UNSUPPORTED, "creation flags need a single-device index");
     if (dim <= 0 || dim > 4096) return set_err(HR_E_INVALID, "dim must be in [1, 4096]");
     if (dtype < F32 || dtype > F16) return set_err(HR_E_INVALID, "dtype must be HR_F32, HR_BF16 or HR_F16");
     if (metric != COSINE && metric != IP && metric != L2) return set_err(HR_E_INVALID, "unknown metric");
@@ -90,6 +97,7 @@ extern "C" int hr_index_create(int dim, int dtype, int metric, int n_dev, const 
         const char* e8 = std::getenv("HIPRAG_SHADOW8");  // 0: no 8-bit shadow (also what a failed allocation leaves)
         h->shadow8 = metric == COSINE && !(e8 && e8[0] == '0');
         h->shadow8_lo = INT64_MAX;
+        if (flags & HR_CREATE_NO_SHADOWS) h->shadow = h->shadow8 = false;  // before the first grow: never allocated
     }
     hipError_t e = hipSetDevice(dev);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
@@ -371,6 +379,86 @@ extern "C" int hr_index_add_device_at(hr_index* h, const float* rows_dev, int64_
     for (int64_t w = 0; w < words; ++w) live += __builtin_popcount(h->live_host[(size_t)w]);
     h->n_live = live;
     return finish_add(h);
+}
+
+// ---------------------------------------------------------------- stored rows, index to index
+// One wave per row: lane c moves the row's 8-element chunks (16 bytes, 2 x 16 for fp32) from the slot of src row Rs
+// to the slot of dst position Rd, bits untouched; lane 0 sets the live bit.  Out-of-range pairs are skipped.
+template <int DT>
+__global__ __launch_bounds__(256) void k_copy_rows(const uint8_t* __restrict__ src, int64_t n_src,
+                                                   uint8_t* __restrict__ dst, int64_t n_dst,
+                                                   const int64_t* __restrict__ src_rows,
+                                                   const int64_t* __restrict__ dst_pos, int64_t n, int S,
+                                                   uint32_t* __restrict__ live) {
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= n) return;
+    const int64_t Rs = src_rows[i], Rd = dst_pos[i];
+    if (Rs < 0 || Rs >= n_src || Rd < 0 || Rd >= n_dst) return;
+    constexpr int64_t CB = DT == F32 ? 2048 : 1024;
+    const int ss = row_slot(Rs), sd = row_slot(Rd);
+    for (int c = lane; c < 2 * S; c += 64) {
+        const int s = c >> 1, h = c & 1;
+        const uint8_t* ps = src + ((Rs >> 5) * S + s) * CB + (ss + 32 * h) * 16;
+        uint8_t* pd = dst + ((Rd >> 5) * S + s) * CB + (sd + 32 * h) * 16;
+        *(u32x4*)pd = *(const u32x4*)ps;
+        if (DT == F32) *(u32x4*)(pd + 1024) = *(const u32x4*)(ps + 1024);
+    }
+    if (lane == 0) atomicOr(&live[Rd >> 5], 1u << (Rd & 31));
+}
+
+// the index holds n_rows_after rows after explicit placement: live count from the device's bits, max norm
+static int finish_placed(hr_index* h, int64_t n_rows_after) {
+    h->n = n_rows_after;
+    const int64_t words = (h->n + 31) / 32;
+    HIP_TRY(hipMemcpyAsync(h->live_host.data(), h->live, (size_t)words * 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    int64_t live = 0;
+    for (int64_t w = 0; w < words; ++w) live += __builtin_popcount(h->live_host[(size_t)w]);
+    h->n_live = live;
+    return finish_add(h);
+}
+
+extern "C" int hr_index_copy_rows(hr_index* dst, hr_index* src, const int64_t* src_rows_dev,
+                                  const int64_t* dst_pos_dev, int64_t n, int64_t n_rows_after, void* stream) {
+    if (!dst || !src || n < 0 || (n > 0 && (!src_rows_dev || !dst_pos_dev))) return set_err(HR_E_INVALID, "bad arguments");
+    if (dst == src) return set_err(HR_E_UNSUPPORTED, "copy_rows needs two different handles");
+    std::scoped_lock lk(dst->mu, src->mu);
+    if (dst->G > 1 || src->G > 1) return set_err(HR_E_UNSUPPORTED, "copy_rows needs single-device handles");
+    if (dst->dim != src->dim || dst->dtype != src->dtype || dst->metric != src->metric || dst->device != src->device)
+        return set_err(HR_E_UNSUPPORTED, "copy_rows needs the same dim, dtype, metric and device on both handles");
+    if (dst->metric == L2) return set_err(HR_E_UNSUPPORTED, "copy_rows supports cosine and dot (inner product)");
+    if (int rc = async_drain(dst)) return rc;  // asynchronous batches in flight read the rows
+    if (n_rows_after < dst->n || n_rows_after > ((int64_t)1 << 32) - 64)
+        return set_err(HR_E_INVALID, "n_rows_after must be >= the current size and < 2^32");
+    if (int rc = set_device(dst)) return rc;
+    if (int rc = index_grow(dst, n_rows_after)) return rc;
+    hipEvent_t ev;  // order after the producer of the row lists on the caller's stream
+    HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    hipError_t e = hipEventRecord(ev, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamWaitEvent(dst->stream, ev, 0);
+    (void)hipEventDestroy(ev);
+    HIP_TRY(e);
+    if (n > 0) {
+        HIP_TRY(hipStreamSynchronize(src->stream));  // (src's writers synchronise before they return: a formality)
+        int rc = dispatch_dt(dst->dtype, [&](auto dt) -> int {
+            hipLaunchKernelGGL((k_copy_rows<decltype(dt)::value>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0,
+                               dst->stream, src->rows, src->n, dst->rows, n_rows_after, src_rows_dev, dst_pos_dev, n,
+                               dst->S, dst->live);
+            HIP_TRY(hipGetLastError());
+            return HR_OK;
+        });
+        if (rc) return rc;
+        shadow_stale(dst, 0);  // (rows placed anywhere)
+        if (src->max_norm2 > dst->max_norm2) {  // the copied rows may include src's largest
+            dst->max_norm2 = src->max_norm2;
+            unsigned long long bits;
+            std::memcpy(&bits, &dst->max_norm2, 8);
+            HIP_TRY(hipMemcpyAsync(dst->norm_bits, &bits, 8, hipMemcpyHostToDevice, dst->stream));
+            HIP_TRY(hipStreamSynchronize(dst->stream));
+        }
+    }
+    return finish_placed(dst, n_rows_after);
 }
 
 extern "C" int hr_gen_rows_device(uint64_t seed, int64_t row0, int64_t n, int dim, float* out_dev, void* stream) {
@@ -2352,6 +2440,10 @@ extern "C" int hr_index_save(hr_index* h, const char* path) {
 }
 
 extern "C" int hr_index_load(const char* path, int n_dev, const int* dev_ids, hr_index** out) {
+    return hr_index_load_ex(path, n_dev, dev_ids, 0, out);
+}
+
+extern "C" int hr_index_load_ex(const char* path, int n_dev, const int* dev_ids, int flags, hr_index** out) {
     if (!path || !out) return set_err(HR_E_INVALID, "bad arguments");
     FILE* f = std::fopen(path, "rb");
     if (!f) return set_err(HR_E_IO, std::string("cannot open ") + path);
@@ -2361,7 +2453,7 @@ extern "C" int hr_index_load(const char* path, int n_dev, const int* dev_ids, hr
         return set_err(HR_E_IO, "not a hiprag index file");
     }
     hr_index* h = nullptr;
-    if (int rc = hr_index_create(hd.dim, hd.dtype, hd.metric, n_dev, dev_ids, &h)) {
+    if (int rc = hr_index_create_ex(hd.dim, hd.dtype, hd.metric, n_dev, dev_ids, flags, &h)) {
         std::fclose(f);
         return rc;
     }

@@ -18,6 +18,11 @@
 // more than an approximate pass here: each probed tile is read once per query either way
 // (lists are rarely probed by two queries of one batch), and 8 fp64 FMAs per 16 bytes keep
 // far below the fp64 VALU rate, so the scan stays HBM-bound.
+//
+// Growable lists (hr_ivf_search_ext): a list is a sequence of extents {first tile, tiles} instead of
+// one tile range, so it can grow at the end of the index without moving the lists after it.  Only
+// the unit list is built differently (k_ivf_units_ext); every other stage is the same code.
+// hr_ivf_position_mask turns a row bitmap by id into the position-order mask the scan takes.
 #include "hr_internal.hpp"
 #include "hr_kernels.hpp"
 
@@ -351,6 +356,92 @@ __global__ __launch_bounds__(1024) void k_ivf_units(const Cand* __restrict__ pro
     if (tid == (int)blockDim.x - 1) uoff[B] = pos < cap ? pos : cap;
 }
 
+// The same over growable lists: list l = the extents ext[e] = {first tile, tiles}, e in [ext_off[l], ext_off[l+1]),
+// list_ntiles[l] tiles in all (the scan's prefix sums read that one word per probe instead of walking the extents).
+// Same unit encoding, query-major order and cap rule.  A list emits exactly list_ntiles[l] units whatever its
+// extents say, and a tile at or beyond n_tiles is replaced by tile 0, so inconsistent tables (a host bug) can
+// neither leave a unit unwritten nor send the scan outside the rows.
+__global__ __launch_bounds__(1024) void k_ivf_units_ext(const Cand* __restrict__ probes, int B, int nprobe,
+                                                        const int64_t* __restrict__ ext_off,
+                                                        const int64_t* __restrict__ ext,
+                                                        const int64_t* __restrict__ list_ntiles, int64_t n_tiles,
+                                                        uint32_t* __restrict__ units, int64_t* __restrict__ uoff,
+                                                        int64_t cap) {
+    __shared__ int64_t part[1024];
+    const int tid = threadIdx.x;
+    const int np = B * nprobe;
+    const int per = (np + blockDim.x - 1) / blockDim.x;  // pairs per thread, contiguous
+    int64_t mine = 0;
+    for (int j = 0; j < per; ++j) {
+        const int p = tid * per + j;
+        if (p >= np) break;
+        const int64_t l = probes[p].row;
+        mine += l >= 0 ? list_ntiles[l] : 0;
+    }
+    int64_t incl = mine;  // exclusive scan over the 1024 partials, as k_ivf_units
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int64_t o = __shfl_up(incl, off, 64);
+        if ((tid & 63) >= off) incl += o;
+    }
+    if ((tid & 63) == 63) part[tid >> 6] = incl;
+    __syncthreads();
+    if (tid < 64) {
+        int64_t w = tid < (int)(blockDim.x >> 6) ? part[tid] : 0;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int64_t o = __shfl_up(w, off, 64);
+            if (tid >= off) w += o;
+        }
+        part[64 + tid] = w;  // inclusive over waves
+    }
+    __syncthreads();
+    int64_t pos = incl - mine + ((tid >> 6) ? part[64 + (tid >> 6) - 1] : 0);
+    for (int j = 0; j < per; ++j) {
+        const int p = tid * per + j;
+        if (p >= np) break;
+        const int b = p / nprobe;
+        if (p % nprobe == 0) uoff[b] = pos < cap ? pos : cap;
+        const int64_t l = probes[p].row;
+        if (l < 0) continue;
+        int64_t left = list_ntiles[l];
+        const int64_t e1 = ext_off[l + 1];
+        for (int64_t e = ext_off[l]; e < e1 && left > 0; ++e) {
+            const int64_t t0 = ext[2 * e];
+            int64_t cnt = ext[2 * e + 1];
+            if (cnt > left) cnt = left;
+            for (int64_t i = 0; i < cnt; ++i, ++pos) {
+                const int64_t t = t0 + i;
+                if (pos < cap) units[pos] = ((uint32_t)b << 26) | (uint32_t)(t >= 0 && t < n_tiles ? t : 0);
+            }
+            left -= cnt > 0 ? cnt : 0;
+        }
+        for (; left > 0; --left, ++pos)
+            if (pos < cap) units[pos] = (uint32_t)b << 26;
+    }
+    if (tid == (int)blockDim.x - 1) uoff[B] = pos < cap ? pos : cap;
+}
+
+// ---------------------------------------------------------------- position mask of an id bitmap
+// One lane per stored position; a wave's ballot is the mask of its two tiles.  Every lane reaches the ballot (a
+// position past the end votes 0), so n_positions need not be a multiple of 32 or 64.
+__global__ __launch_bounds__(256) void k_ivf_position_mask(const int64_t* __restrict__ ids, int64_t n_positions,
+                                                           const uint64_t* __restrict__ row_mask, int64_t n_mask_rows,
+                                                           uint32_t* __restrict__ out) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    bool on = false;
+    if (p < n_positions) {
+        const int64_t id = ids[p];
+        if (id >= 0 && id < n_mask_rows) on = (row_mask[id >> 6] >> (id & 63)) & 1ull;
+    }
+    const unsigned long long vote = __ballot(on);
+    const int lane = threadIdx.x & 63;
+    const int64_t w = (p - lane) >> 5;  // first of the wave's two words
+    const int64_t n_words = (n_positions + 31) >> 5;
+    if (lane == 0 && w < n_words) out[w] = (uint32_t)vote;
+    if (lane == 32 && w + 1 < n_words) out[w + 1] = (uint32_t)(vote >> 32);
+}
+
 // ---------------------------------------------------------------- K12: exact scan of the units
 // One wave per unit at a time (static contiguous split of the unit list).  Lane l = r + 32h of a
 // k-step chunk holds elements 16s + 8h + j of row r, i.e. canonical partials c = 16(s%4) + 8h + j;
@@ -488,11 +579,17 @@ __global__ void k_fill_f64(double* __restrict__ p, int n, double v) {
 }  // namespace
 
 // ---------------------------------------------------------------- C ABI
-extern "C" int hr_ivf_search(hr_index* h, const float* centroids_dev, int nlist, const int64_t* list_tiles_dev,
-                             int64_t max_list_tiles, const int64_t* ids_dev, const float* q_dev, int B, int nprobe,
-                             int k, const uint64_t* row_mask_dev, void* cand_out_dev, double* bound_out_dev,
-                             void* probes_out_dev, void* stream) {
-    if (!h || !centroids_dev || !list_tiles_dev || !ids_dev || !q_dev || !cand_out_dev || !bound_out_dev)
+// The lists of one search: contiguous (list_tiles, hr_ivf_search) or extents (hr_ivf_search_ext)
+struct IvfLists {
+    const int64_t* list_tiles = nullptr;
+    const int64_t *ext_off = nullptr, *ext = nullptr, *list_ntiles = nullptr;
+};
+
+static int ivf_search(hr_index* h, const float* centroids_dev, int nlist, const IvfLists& lists,
+                      int64_t max_list_tiles, const int64_t* ids_dev, const float* q_dev, int B, int nprobe, int k,
+                      const uint64_t* row_mask_dev, void* cand_out_dev, double* bound_out_dev, void* probes_out_dev,
+                      void* stream) {
+    if (!h || !centroids_dev || !ids_dev || !q_dev || !cand_out_dev || !bound_out_dev)
         return set_err(HR_E_INVALID, "null argument");
     if (h->G > 1) return set_err(HR_E_UNSUPPORTED, "IVF lists need a single-device index");
     if (B <= 0 || nlist <= 0 || nprobe <= 0 || nprobe > nlist || nprobe > kTopkMax || k <= 0 || k > kTopkMax ||
@@ -542,8 +639,13 @@ extern "C" int hr_ivf_search(hr_index* h, const float* centroids_dev, int nlist,
                            centroids_dev, nlist, dpad, sc.q32.as<float>(), bc, qgroup, h->ivf_coarse.as<Cand>());
         hipLaunchKernelGGL(k_topk_cand, dim3(bc), dim3(1024), 0, st, h->ivf_coarse.as<Cand>(), (const int64_t*)nullptr,
                            1, (int64_t)nlist, bc, nprobe, h->ivf_probe.as<Cand>());
-        hipLaunchKernelGGL(k_ivf_units, dim3(1), dim3(1024), 0, st, h->ivf_probe.as<Cand>(), bc, nprobe,
-                           list_tiles_dev, h->ivf_units.as<uint32_t>(), h->ivf_uoff.as<int64_t>(), cap);
+        if (lists.list_tiles)
+            hipLaunchKernelGGL(k_ivf_units, dim3(1), dim3(1024), 0, st, h->ivf_probe.as<Cand>(), bc, nprobe,
+                               lists.list_tiles, h->ivf_units.as<uint32_t>(), h->ivf_uoff.as<int64_t>(), cap);
+        else
+            hipLaunchKernelGGL(k_ivf_units_ext, dim3(1), dim3(1024), 0, st, h->ivf_probe.as<Cand>(), bc, nprobe,
+                               lists.ext_off, lists.ext, lists.list_ntiles, (h->n + 31) / 32,
+                               h->ivf_units.as<uint32_t>(), h->ivf_uoff.as<int64_t>(), cap);
         HIP_TRY(hipGetLastError());
         const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((int64_t)h->n_cu * 8, (cap + 3) / 4));
         int rc = dispatch_dt(h->dtype, [&](auto dt) -> int {
@@ -576,6 +678,44 @@ extern "C" int hr_ivf_search(hr_index* h, const float* centroids_dev, int nlist,
     }
     // exact over the visible rows: nothing unreturned can matter
     hipLaunchKernelGGL(k_fill_f64, dim3((B + 255) / 256), dim3(256), 0, st, bound_out_dev, B, -INFINITY);
+    HIP_TRY(hipGetLastError());
+    return HR_OK;
+}
+
+extern "C" int hr_ivf_search(hr_index* h, const float* centroids_dev, int nlist, const int64_t* list_tiles_dev,
+                             int64_t max_list_tiles, const int64_t* ids_dev, const float* q_dev, int B, int nprobe,
+                             int k, const uint64_t* row_mask_dev, void* cand_out_dev, double* bound_out_dev,
+                             void* probes_out_dev, void* stream) {
+    if (!list_tiles_dev) return set_err(HR_E_INVALID, "null argument");
+    IvfLists lists;
+    lists.list_tiles = list_tiles_dev;
+    return ivf_search(h, centroids_dev, nlist, lists, max_list_tiles, ids_dev, q_dev, B, nprobe, k, row_mask_dev,
+                      cand_out_dev, bound_out_dev, probes_out_dev, stream);
+}
+
+extern "C" int hr_ivf_search_ext(hr_index* h, const float* centroids_dev, int nlist, const int64_t* ext_off_dev,
+                                 const int64_t* ext_dev, const int64_t* list_ntiles_dev, int64_t max_list_tiles,
+                                 const int64_t* ids_dev, const float* q_dev, int B, int nprobe, int k,
+                                 const uint64_t* row_mask_dev, void* cand_out_dev, double* bound_out_dev,
+                                 void* probes_out_dev, void* stream) {
+    // (ext_dev may be null: an index whose lists have no extent yet)
+    if (!ext_off_dev || !list_ntiles_dev) return set_err(HR_E_INVALID, "null argument");
+    IvfLists lists;
+    lists.ext_off = ext_off_dev;
+    lists.ext = ext_dev;
+    lists.list_ntiles = list_ntiles_dev;
+    return ivf_search(h, centroids_dev, nlist, lists, max_list_tiles, ids_dev, q_dev, B, nprobe, k, row_mask_dev,
+                      cand_out_dev, bound_out_dev, probes_out_dev, stream);
+}
+
+extern "C" int hr_ivf_position_mask(const int64_t* ids_dev, int64_t n_positions, const uint64_t* row_mask_dev,
+                                    int64_t n_mask_rows, uint32_t* out_dev, void* stream) {
+    if (n_positions < 0 || n_mask_rows < 0 || (n_positions > 0 && (!ids_dev || !out_dev)) ||
+        (n_mask_rows > 0 && !row_mask_dev))
+        return set_err(HR_E_INVALID, "bad arguments");
+    if (n_positions == 0) return HR_OK;
+    hipLaunchKernelGGL(k_ivf_position_mask, dim3((unsigned)((n_positions + 255) / 256)), dim3(256), 0,
+                       (hipStream_t)stream, ids_dev, n_positions, row_mask_dev, n_mask_rows, out_dev);
     HIP_TRY(hipGetLastError());
     return HR_OK;
 }

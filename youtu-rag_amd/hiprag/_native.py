@@ -20,6 +20,7 @@ DTYPES = {"f32": 0, "float32": 0, "fp32": 0, "bf16": 1, "bfloat16": 1, "f16": 2,
 METRICS = {"cosine": 0, "ip": 1, "dot": 1, "euclidean": 2, "l2": 2}
 HR_MAX_K = 128   # include/hiprag.h
 HR_MAX_KC = 256
+HR_CREATE_NO_SHADOWS = 1
 HR_LEX_TERM_BITS = 22    # term id = crc32(token) % 2**22
 HR_LEX_MAX_QTERMS = 64
 HR_LEX_MAX_K = 1024
@@ -54,7 +55,8 @@ EXPORTS = [
     "hr_index_search_shard_exact", "hr_merge_sorted", "hr_memcpy_async", "hr_attn_varlen", "hr_gelu_erf",
     "hr_lex_pack", "hr_lex_create", "hr_lex_destroy", "hr_lex_add", "hr_lex_remove", "hr_lex_size", "hr_lex_stats",
     "hr_lex_df", "hr_lex_search", "hr_lex_last_ms", "hr_index_set_shadow8", "hr_index_debug_approx8",
-    "hr_index_shadow8_stats",
+    "hr_index_shadow8_stats", "hr_index_create_ex", "hr_index_load_ex", "hr_index_copy_rows", "hr_ivf_search_ext",
+    "hr_ivf_position_mask",
 ]
 
 _lib = None
@@ -124,6 +126,11 @@ def load_library(path: str | None = None):
         pp = ctypes.POINTER(ctypes.c_void_p)
         sig = {
             "hr_index_create": [i32, i32, i32, i32, vp, pp],
+            "hr_index_create_ex": [i32, i32, i32, i32, vp, i32, pp],
+            "hr_index_load_ex": [ctypes.c_char_p, i32, vp, i32, pp],
+            "hr_index_copy_rows": [vp, vp, vp, vp, i64, i64, vp],
+            "hr_ivf_search_ext": [vp, vp, i32, vp, vp, vp, i64, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp],
+            "hr_ivf_position_mask": [vp, i64, vp, i64, vp, vp],
             "hr_index_reserve": [vp, i64],
             "hr_index_add": [vp, vp, i64, vp],
             "hr_index_add_synthetic": [vp, u64, i64, i64, vp],
@@ -241,9 +248,11 @@ class NativeIndex:
     """One device shard of the vector index (an hr_index handle)."""
 
     def __init__(self, dim: int, dtype: str = "bf16", metric: str = "cosine", device: int = 0,
-                 devices: list[int] | None = None, _handle=None):
+                 devices: list[int] | None = None, _handle=None, no_shadows: bool = False):
         """One index handle.  ``devices`` (GPU ids, repeats allowed) shards its rows over several
-        GPUs inside the handle (hr_index_create with n_dev > 1); default: the single ``device``."""
+        GPUs inside the handle (hr_index_create with n_dev > 1); default: the single ``device``.
+        ``no_shadows``: keep no 16-bit / 8-bit scan shadow (HR_CREATE_NO_SHADOWS: an index that is
+        never scanned by the exact search, such as IVF lists)."""
         self.lib = load_library()
         self.devices = [int(d) for d in devices] if devices else [int(device)]
         self.dim, self.dtype, self.metric, self.device = int(dim), dtype, metric, self.devices[0]
@@ -256,8 +265,8 @@ class NativeIndex:
             raise ValueError(f"unknown metric {metric!r}")
         h = ctypes.c_void_p()
         dev = (ctypes.c_int * len(self.devices))(*self.devices)
-        _check(self.lib.hr_index_create(self.dim, DTYPES[dtype], METRICS[metric], len(self.devices), dev,
-                                        ctypes.byref(h)))
+        _check(self.lib.hr_index_create_ex(self.dim, DTYPES[dtype], METRICS[metric], len(self.devices), dev,
+                                           HR_CREATE_NO_SHADOWS if no_shadows else 0, ctypes.byref(h)))
         self._h = h
 
     # -- lifecycle
@@ -307,6 +316,26 @@ class NativeIndex:
                                       ctypes.c_void_p(mask_ptr or None), ctypes.c_void_p(cand_ptr),
                                       ctypes.c_void_p(bound_ptr), ctypes.c_void_p(probes_ptr or None),
                                       ctypes.c_void_p(stream or None)))
+
+    def ivf_search_ext(self, centroids_ptr: int, nlist: int, ext_off_ptr: int, ext_ptr: int, list_ntiles_ptr: int,
+                       max_list_tiles: int, ids_ptr: int, q_ptr: int, B: int, nprobe: int, k: int, cand_ptr: int,
+                       bound_ptr: int, probes_ptr: int = 0, mask_ptr: int = 0, stream: int = 0) -> None:
+        """ivf_search over lists given as extents (hr_ivf_search_ext)."""
+        _check(self.lib.hr_ivf_search_ext(self._h, ctypes.c_void_p(centroids_ptr), int(nlist),
+                                          ctypes.c_void_p(ext_off_ptr), ctypes.c_void_p(ext_ptr or None),
+                                          ctypes.c_void_p(list_ntiles_ptr), int(max_list_tiles),
+                                          ctypes.c_void_p(ids_ptr), ctypes.c_void_p(q_ptr), int(B), int(nprobe),
+                                          int(k), ctypes.c_void_p(mask_ptr or None), ctypes.c_void_p(cand_ptr),
+                                          ctypes.c_void_p(bound_ptr), ctypes.c_void_p(probes_ptr or None),
+                                          ctypes.c_void_p(stream or None)))
+
+    def copy_rows_from(self, src: "NativeIndex", src_rows_ptr: int, dst_pos_ptr: int, n: int, n_rows_after: int,
+                       stream: int = 0) -> None:
+        """Copy the stored bits of n rows of ``src`` (int64 device row numbers) to the int64 device positions of
+        this index (hr_index_copy_rows)."""
+        _check(self.lib.hr_index_copy_rows(self._h, src._h, ctypes.c_void_p(int(src_rows_ptr) or None),
+                                           ctypes.c_void_p(int(dst_pos_ptr) or None), int(n), int(n_rows_after),
+                                           ctypes.c_void_p(int(stream) or None)))
 
     def add_synthetic(self, seed: int, global_row0: int, n: int) -> int:
         first = ctypes.c_int64(0)
@@ -556,12 +585,14 @@ class NativeIndex:
 
     @classmethod
     def load(cls, path: str, device: int = 0, dim: int | None = None, dtype: str | None = None,
-             metric: str | None = None, devices: list[int] | None = None) -> "NativeIndex":
+             metric: str | None = None, devices: list[int] | None = None, no_shadows: bool = False
+             ) -> "NativeIndex":
         L = load_library()
         h = ctypes.c_void_p()
         devs = [int(d) for d in devices] if devices else [int(device)]
         dev = (ctypes.c_int * len(devs))(*devs)
-        _check(L.hr_index_load(os.fsencode(path), len(devs), dev, ctypes.byref(h)))
+        _check(L.hr_index_load_ex(os.fsencode(path), len(devs), dev, HR_CREATE_NO_SHADOWS if no_shadows else 0,
+                                  ctypes.byref(h)))
         d, dt, m, g = (ctypes.c_int(0) for _ in range(4))
         _check(L.hr_index_info(h, ctypes.byref(d), ctypes.byref(dt), ctypes.byref(m), ctypes.byref(g)))
         # the file's own shape (the dim / dtype / metric arguments are only checked against it)
@@ -677,6 +708,14 @@ def gen_rows_device(seed: int, row0: int, n: int, dim: int, out_ptr: int, stream
     """Synthetic corpus rows [row0, row0 + n) as fp32 into device memory (the hr_index_add_synthetic generator)."""
     _check(load_library().hr_gen_rows_device(int(seed), int(row0), int(n), int(dim), ctypes.c_void_p(out_ptr),
                                              ctypes.c_void_p(stream or None)))
+
+
+def ivf_position_mask(ids_ptr: int, n_positions: int, row_mask_ptr: int, n_mask_rows: int, out_ptr: int,
+                      stream: int = 0) -> None:
+    """uint32-per-tile position mask of a by-id uint64 bitmap, all on the device (hr_ivf_position_mask)."""
+    _check(load_library().hr_ivf_position_mask(ctypes.c_void_p(ids_ptr or None), int(n_positions),
+                                               ctypes.c_void_p(row_mask_ptr or None), int(n_mask_rows),
+                                               ctypes.c_void_p(out_ptr or None), ctypes.c_void_p(stream or None)))
 
 
 def topk_records(in_ptr: int, B: int, m: int, out_ptr: int, seg_stride: int = 0, seg_off_ptr: int = 0,

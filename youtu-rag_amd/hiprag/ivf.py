@@ -17,11 +17,19 @@ about ``B * nprobe / nlist`` of the corpus instead of all of it.
 
 Training (spherical k-means for cosine, max-inner-product k-means for dot) and list assignment
 are build-time GEMMs and run through PyTorch (hipBLASLt); only the search is on the query path.
+Growth: a bulk-built index keeps one contiguous tile range per list (``list_tiles``, ``hr_ivf_search``).  The
+first incremental ``add`` switches it to *extents*: every list is a sequence of (first tile, tile count) ranges,
+new ranges are allocated at the end of the index (``plan_add``), and the search goes through
+``hr_ivf_search_ext``.  ``remove`` tombstones positions, ``compact`` rebuilds one extent per list without dead
+rows, ``save`` / ``load`` persist rows and tables.  Results stay those of the oracle's restatement.
+
 Multi-GPU: every rank holds its row shard's share of every list (shared centroids), returns its
 exact top-k of its visible rows with bound -inf, and ``IvfShardedSearch`` merges them with the
 same packed all-gather + merge as the exact search.
 """
 from __future__ import annotations
+
+import os
 
 import numpy as np
 
@@ -31,6 +39,55 @@ from .dist import ShardedSearch
 
 def _round64(d: int) -> int:
     return (d + 63) // 64 * 64
+
+
+def plan_add(counts, caps, tails, ntiles, next_tile: int, new_lists, nlist: int | None = None):
+    """Placement of one ``add`` call (pure, host, deterministic).
+
+    State per list: ``counts`` slots used (live or tombstoned), ``caps`` slots allocated (32 per tile), ``tails``
+    the position of the next free slot (meaningful where counts < caps: a list's free slots are the end of its
+    last extent), ``ntiles`` tiles allocated; ``next_tile`` is the first unallocated tile of the index.
+    ``new_lists[i]`` is the list of the call's i-th row.
+
+    Within a list the rows keep the order of the call: they first fill the free slots, and what does not fit goes
+    to ONE new extent of max(tiles needed, ceil(ntiles / 8), 1) tiles (so trickle adds do not fragment without
+    bound); new extents are allocated at the end of the index in ascending list order.
+
+    Returns (dest int64 (m,), new_ext int64 (j, 3) rows of (list, first tile, tiles), counts, caps, tails, ntiles,
+    next_tile) -- the arrays are new, the inputs are left alone."""
+    counts, caps, tails, ntiles = (np.asarray(a, np.int64) for a in (counts, caps, tails, ntiles))
+    new_lists = np.asarray(new_lists, np.int64).reshape(-1)
+    nl = len(counts) if nlist is None else int(nlist)
+    m = len(new_lists)
+    if m and (new_lists.min() < 0 or new_lists.max() >= nl):
+        raise ValueError("list out of range")
+    add = np.bincount(new_lists, minlength=nl).astype(np.int64)
+    free = caps - counts
+    over = np.maximum(add - free, 0)
+    grow = np.where(over > 0, np.maximum(np.maximum((over + 31) // 32, (ntiles + 7) // 8), 1), 0)
+    first = int(next_tile) + np.cumsum(grow) - grow          # (ascending list order)
+    order = np.argsort(new_lists, kind="stable")
+    start = np.cumsum(add) - add
+    rank = np.empty(m, np.int64)
+    rank[order] = np.arange(m, dtype=np.int64) - start[new_lists[order]]
+    fits = rank < free[new_lists]
+    dest = np.where(fits, tails[new_lists] + rank, first[new_lists] * 32 + rank - free[new_lists])
+    grown = np.nonzero(grow)[0]
+    new_ext = np.stack([grown, first[grown], grow[grown]], axis=1).astype(np.int64) if len(grown) else \
+        np.zeros((0, 3), np.int64)
+    tails2 = np.where(over > 0, first * 32 + over, tails + add)
+    return dest, new_ext, counts + add, caps + 32 * grow, tails2, ntiles + grow, int(next_tile) + int(grow.sum())
+
+
+def _extent_positions(first, nt):
+    """Positions of the extents (first tile, tiles) in order, concatenated."""
+    first, nt = np.asarray(first, np.int64), np.asarray(nt, np.int64)
+    n = nt * 32
+    total = int(n.sum())
+    if total == 0:
+        return np.zeros(0, np.int64)
+    base = np.repeat(first * 32 - (np.cumsum(n) - n), n)
+    return base + np.arange(total, dtype=np.int64)
 
 
 class IvfIndex:
@@ -47,12 +104,24 @@ class IvfIndex:
         self.dev = torch.device("cuda", device)
         self.device = device
         self.dpad = _round64(self.dim)
-        self.index = _native.NativeIndex(self.dim, dtype, self.metric, device)
+        # list-order rows are never scanned by the exact search: no scan shadows
+        self.index = _native.NativeIndex(self.dim, dtype, self.metric, device, no_shadows=True)
         self.centroids = None      # (nlist, dpad) fp32, processed (unit norm for cosine)
         self.list_tiles = None     # (nlist + 1,) int64 tile offsets
         self.ids = None            # (positions,) int64 original id per stored position, -1 for pads
         self.max_list_tiles = 0
         self.n = 0
+        self.id_base = 0            # lists_of_rows / pos_of_id are indexed by id - id_base
+        self.lists_of_rows = None   # (ids,) int64 device: list of the row with that id, -1 = none
+        self.pos_of_id = None       # (ids,) int64 host: stored position of that id, -1 = none
+        # extent form (after the first incremental add, compact() or load()); host tables are the truth, the
+        # device copies (ext_off, ext, list_ntiles) are rebuilt after every change
+        self.extents = False
+        self.ext_list = self.ext_first = self.ext_nt = None   # host, creation order
+        self.counts = self.caps = self.tails = self.ntiles = None
+        self.next_tile = 0
+        self.ext_off = self.ext = self.list_ntiles = None     # device
+        self._ids_buf = None
 
     # ---------------------------------------------------------------- build
     def _process(self, x):
@@ -98,8 +167,8 @@ class IvfIndex:
         torch = self.torch
         if self.centroids is None:
             raise RuntimeError("train() the coarse quantizer first")
-        if self.n:
-            raise RuntimeError("IVF lists are built once (bulk); create a new index to rebuild")
+        if self.n or self.extents:
+            raise RuntimeError("build() is the bulk path of an empty index; use add() to grow it")
         cent = self.centroids[:, : self.dim]
         lists = torch.empty(n, dtype=torch.int64, device=self.dev)
         for i in range(0, n, chunk):
@@ -128,6 +197,7 @@ class IvfIndex:
         self.max_list_tiles = int(tiles.max().item()) if n else 0
         self.n = n
         self.lists_of_rows = lists  # row -> list (tests, the oracle restatement)
+        self.id_base = int(id_offset)
         return self
 
     def build_synthetic(self, seed: int, row0: int, n: int, chunk: int = 1 << 18):
@@ -144,8 +214,16 @@ class IvfIndex:
 
     def list_members(self) -> list[np.ndarray]:
         """Original ids of every list (host; tests and diagnostics)."""
-        lt = self.list_tiles.cpu().numpy()
         ids = self.ids.cpu().numpy()
+        if self.extents:
+            order = np.argsort(self.ext_list, kind="stable")
+            out = []
+            for l in range(self.nlist):
+                e = order[self.ext_list[order] == l]
+                got = ids[_extent_positions(self.ext_first[e], self.ext_nt[e])]
+                out.append(got[got >= 0])
+            return out
+        lt = self.list_tiles.cpu().numpy()
         return [ids[lt[l] * 32: lt[l + 1] * 32][ids[lt[l] * 32: lt[l + 1] * 32] >= 0] for l in range(self.nlist)]
 
     # ---------------------------------------------------------------- search
@@ -157,6 +235,13 @@ class IvfIndex:
             raise RuntimeError("build() the index first")
         st = stream if stream is not None else torch.cuda.current_stream(self.dev).cuda_stream
         q = q.contiguous()
+        if self.extents:
+            self.index.ivf_search_ext(self.centroids.data_ptr(), self.nlist, self.ext_off.data_ptr(),
+                                      self.ext.data_ptr() if self.ext.numel() else 0, self.list_ntiles.data_ptr(),
+                                      self.max_list_tiles, self.ids.data_ptr(), q.data_ptr(), q.shape[0], nprobe, k,
+                                      cand.data_ptr(), bound.data_ptr(), 0 if probes is None else probes.data_ptr(),
+                                      mask_ptr, st)
+            return
         self.index.ivf_search(self.centroids.data_ptr(), self.nlist, self.list_tiles.data_ptr(), self.max_list_tiles,
                               self.ids.data_ptr(), q.data_ptr(), q.shape[0], nprobe, k, cand.data_ptr(),
                               bound.data_ptr(), 0 if probes is None else probes.data_ptr(), mask_ptr, st)
@@ -171,6 +256,281 @@ class IvfIndex:
         s = cand[..., 0].to(torch.float32)
         r = cand.view(torch.int64)[..., 1].clone()
         return s, r
+
+    # ---------------------------------------------------------------- growth
+    @property
+    def n_ext(self) -> int:
+        return len(self.ext_list) if self.extents else self.nlist
+
+    @property
+    def n_positions(self) -> int:
+        """Stored positions (32 per allocated tile)."""
+        return int(self.ids.shape[0]) if self.ids is not None else 0
+
+    def n_dead(self) -> int:
+        """Used slots that hold a removed row (what compact() reclaims)."""
+        used = int(self.counts.sum()) if self.extents else self.n
+        return used - self.index.size()[1]
+
+    def _grow_id_maps(self, n_ids: int):
+        torch = self.torch
+        have = 0 if self.pos_of_id is None else len(self.pos_of_id)
+        if n_ids <= have:
+            return
+        pos = np.full(n_ids, -1, np.int64)
+        lst = torch.full((n_ids,), -1, dtype=torch.int64, device=self.dev)
+        if have:
+            pos[:have] = self.pos_of_id
+            lst[:have] = self.lists_of_rows
+        self.pos_of_id, self.lists_of_rows = pos, lst
+
+    def _to_extents(self):
+        """Switch to the extent tables (idempotent): a bulk-built index becomes one extent per list."""
+        if self.extents:
+            return
+        nl = self.nlist
+        if self.ids is not None:  # bulk built
+            lt = self.list_tiles.cpu().numpy().astype(np.int64)
+            ids = self.ids.cpu().numpy()
+            cnt = np.bincount(self.lists_of_rows.cpu().numpy(), minlength=nl).astype(np.int64) if self.n else \
+                np.zeros(nl, np.int64)
+            self.ext_list, self.ext_first, self.ext_nt = np.arange(nl, dtype=np.int64), lt[:-1].copy(), np.diff(lt)
+            self.counts, self.ntiles = cnt, np.diff(lt)
+            self.next_tile = int(lt[-1])
+            pos = np.full(self.n, -1, np.int64)
+            live = np.nonzero(ids[: self.next_tile * 32] >= 0)[0]
+            pos[ids[live] - self.id_base] = live
+            self.pos_of_id = pos
+            self._ids_buf = self.ids[: self.next_tile * 32]
+        else:
+            self.ext_list = self.ext_first = self.ext_nt = np.zeros(0, np.int64)
+            self.counts, self.ntiles = np.zeros(nl, np.int64), np.zeros(nl, np.int64)
+            self.next_tile = 0
+            self.pos_of_id = np.zeros(0, np.int64)
+            self.lists_of_rows = self.torch.zeros(0, dtype=self.torch.int64, device=self.dev)
+            self._ids_buf = self.torch.zeros(0, dtype=self.torch.int64, device=self.dev)
+        self.caps = self.ntiles * 32
+        self.tails = self.ext_first[:nl] * 32 + self.counts if len(self.ext_first) else np.zeros(nl, np.int64)
+        self.extents = True
+        self.list_tiles = None
+        self._sync_tables()
+
+    def _sync_tables(self):
+        """Device copies of the extent tables (CSR by list, creation order inside a list) and the ids view."""
+        torch = self.torch
+        order = np.argsort(self.ext_list, kind="stable")
+        off = np.zeros(self.nlist + 1, np.int64)
+        off[1:] = np.cumsum(np.bincount(self.ext_list, minlength=self.nlist))
+        ext = np.stack([self.ext_first[order], self.ext_nt[order]], axis=1) if len(order) else np.zeros((0, 2), np.int64)
+        self.ext_off = torch.from_numpy(off).to(self.dev)
+        self.ext = torch.from_numpy(np.ascontiguousarray(ext)).to(self.dev)
+        self.list_ntiles = torch.from_numpy(self.ntiles.copy()).to(self.dev)
+        self.max_list_tiles = int(self.ntiles.max()) if self.nlist else 0
+        total = self.next_tile * 32
+        if self._ids_buf.shape[0] < total:  # (amortised: the buffer grows by half)
+            buf = torch.full((max(total, self._ids_buf.shape[0] * 3 // 2),), -1, dtype=torch.int64, device=self.dev)
+            buf[: self._ids_buf.shape[0]] = self._ids_buf
+            self._ids_buf = buf
+        self.ids = self._ids_buf[: max(total, 1)] if self._ids_buf.shape[0] >= max(total, 1) else \
+            torch.full((1,), -1, dtype=torch.int64, device=self.dev)
+
+    def _place(self, lists: np.ndarray, ids: np.ndarray):
+        """Plan the placement of rows with the given lists / ids and install the tables; returns (dest device
+        tensor, positions after)."""
+        torch = self.torch
+        if self.next_tile * 32 + len(ids) + 32 * self.nlist > (1 << 31):
+            raise ValueError("an IVF index holds at most 2^31 positions")
+        rel = ids - self.id_base
+        if len(rel) and rel.min() < 0:
+            raise ValueError(f"ids below the index's id base {self.id_base}")
+        if len(np.unique(rel)) != len(rel):
+            raise ValueError("duplicate ids inside one add")
+        self._grow_id_maps(int(rel.max()) + 1 if len(rel) else 0)
+        if len(rel) and (self.pos_of_id[rel] >= 0).any():
+            raise ValueError("an id of this add is already stored")
+        dest, new_ext, self.counts, self.caps, self.tails, self.ntiles, self.next_tile = plan_add(
+            self.counts, self.caps, self.tails, self.ntiles, self.next_tile, lists)
+        if len(new_ext):
+            self.ext_list = np.concatenate([self.ext_list, new_ext[:, 0]])
+            self.ext_first = np.concatenate([self.ext_first, new_ext[:, 1]])
+            self.ext_nt = np.concatenate([self.ext_nt, new_ext[:, 2]])
+        self._sync_tables()
+        self.pos_of_id[rel] = dest
+        dest_d = torch.from_numpy(dest).to(self.dev)
+        rel_d = torch.from_numpy(rel).to(self.dev)
+        self.ids[dest_d] = torch.from_numpy(ids).to(self.dev)
+        self.lists_of_rows[rel_d] = torch.from_numpy(np.asarray(lists, np.int64)).to(self.dev)
+        self.n += len(ids)
+        return dest_d, self.next_tile * 32
+
+    def _ids_arg(self, ids, m: int) -> np.ndarray:
+        if ids is None:
+            have = 0 if self.pos_of_id is None else len(self.pos_of_id)
+            return np.arange(have, have + m, dtype=np.int64) + self.id_base
+        if hasattr(ids, "cpu"):
+            ids = ids.cpu().numpy()
+        ids = np.ascontiguousarray(np.asarray(ids, np.int64).reshape(-1))
+        if len(ids) != m:
+            raise ValueError("one id per row")
+        return ids
+
+    def add(self, rows, ids=None):
+        """Add a (m, dim) fp32 device tensor of raw vectors with their ids (default: the next ids), after train(),
+        with or without an earlier build().  Returns the lists the rows went to (host)."""
+        torch = self.torch
+        if self.centroids is None:
+            raise RuntimeError("train() the coarse quantizer first")
+        rows = rows.to(self.dev, torch.float32).contiguous()
+        if rows.dim() != 2 or rows.shape[1] != self.dim:
+            raise ValueError(f"rows must be (m, {self.dim})")
+        self._to_extents()
+        ids = self._ids_arg(ids, rows.shape[0])
+        if not len(ids):
+            return np.zeros(0, np.int64)
+        lists = self._assign(self._process(rows), self.centroids[:, : self.dim]).cpu().numpy()
+        dest, total = self._place(lists, ids)
+        stream = torch.cuda.current_stream(self.dev).cuda_stream
+        self.index.add_device_at(rows.data_ptr(), rows.shape[0], dest.data_ptr(), total, stream=stream)
+        return lists
+
+    def add_from(self, src_index, src_rows, ids=None, lists=None, chunk: int = 1 << 16):
+        """The same placement for rows already stored in ``src_index`` (a NativeIndex of the same dim, dtype and
+        metric on this device): their stored bits are copied (hr_index_copy_rows), not normalised and rounded a
+        second time.  ``ids`` default to the source row numbers; ``lists`` (optional) skips the assignment, which
+        otherwise runs on the stored vectors."""
+        torch = self.torch
+        if self.centroids is None:
+            raise RuntimeError("train() the coarse quantizer first")
+        src_rows = np.ascontiguousarray(np.asarray(src_rows, np.int64).reshape(-1))
+        ids = src_rows.copy() if ids is None else self._ids_arg(ids, len(src_rows))
+        self._to_extents()
+        if not len(src_rows):
+            return np.zeros(0, np.int64)
+        if lists is None:
+            cent = self.centroids[:, : self.dim]
+            parts = []
+            for i in range(0, len(src_rows), chunk):
+                x = torch.from_numpy(src_index.get_rows(src_rows[i:i + chunk])).to(self.dev)
+                parts.append(self._assign(self._process(x), cent).cpu().numpy())
+            lists = np.concatenate(parts)
+        lists = np.ascontiguousarray(np.asarray(lists, np.int64).reshape(-1))
+        dest, total = self._place(lists, ids)
+        src_d = torch.from_numpy(src_rows).to(self.dev)
+        stream = torch.cuda.current_stream(self.dev).cuda_stream
+        self.index.copy_rows_from(src_index, src_d.data_ptr(), dest.data_ptr(), len(src_rows), total, stream=stream)
+        return lists
+
+    def remove(self, ids):
+        """Tombstone the rows with these ids (unknown or already removed ids: no-op).  Returns the number removed."""
+        torch = self.torch
+        if hasattr(ids, "cpu"):
+            ids = ids.cpu().numpy()
+        rel = np.unique(np.asarray(ids, np.int64).reshape(-1)) - self.id_base
+        if self.ids is None or not len(rel):
+            return 0
+        self._to_extents()
+        rel = rel[(rel >= 0) & (rel < len(self.pos_of_id))]
+        rel = rel[self.pos_of_id[rel] >= 0]
+        if not len(rel):
+            return 0
+        pos = self.pos_of_id[rel]
+        self.index.remove(pos)
+        self.pos_of_id[rel] = -1
+        self.ids[torch.from_numpy(pos).to(self.dev)] = -1
+        self.lists_of_rows[torch.from_numpy(rel).to(self.dev)] = -1
+        self.n -= len(rel)
+        return len(rel)
+
+    def compact(self):
+        """Rebuild into a fresh list-order index: one extent per list, no dead rows (stored bits copied)."""
+        torch = self.torch
+        self._to_extents()
+        order = np.argsort(self.ext_list, kind="stable")
+        pos = _extent_positions(self.ext_first[order], self.ext_nt[order])   # list by list, fill order inside
+        lst = np.repeat(self.ext_list[order], self.ext_nt[order] * 32)
+        ids = self.ids.cpu().numpy() if len(pos) else np.zeros(0, np.int64)
+        keep = ids[pos] >= 0 if len(pos) else np.zeros(0, bool)
+        pos, lst = pos[keep], lst[keep]
+        nl = self.nlist
+        cnt = np.bincount(lst, minlength=nl).astype(np.int64)
+        nt = (cnt + 31) // 32
+        first = np.cumsum(nt) - nt
+        start = np.cumsum(cnt) - cnt
+        dest = first[lst] * 32 + np.arange(len(pos), dtype=np.int64) - start[lst]
+        total = int(nt.sum()) * 32
+        fresh = _native.NativeIndex(self.dim, self.dtype, self.metric, self.device, no_shadows=True)
+        new_ids = torch.full((max(total, 1),), -1, dtype=torch.int64, device=self.dev)
+        if len(pos):
+            src_d, dst_d = torch.from_numpy(pos).to(self.dev), torch.from_numpy(dest).to(self.dev)
+            fresh.reserve(total)
+            fresh.copy_rows_from(self.index, src_d.data_ptr(), dst_d.data_ptr(), len(pos), total,
+                                 stream=torch.cuda.current_stream(self.dev).cuda_stream)
+            new_ids[dst_d] = self.ids[src_d]
+            self.pos_of_id[ids[pos] - self.id_base] = dest
+        self.index.close()
+        self.index = fresh
+        self.ext_list, self.ext_first, self.ext_nt = np.arange(nl, dtype=np.int64), first, nt
+        self.counts, self.ntiles, self.caps = cnt, nt.copy(), nt * 32
+        self.tails = first * 32 + cnt
+        self.next_tile = int(nt.sum())
+        self._ids_buf = new_ids
+        self._sync_tables()
+        return self
+
+    # ---------------------------------------------------------------- persistence
+    def save(self, path: str):
+        """The list-order rows to ``path`` (hr_index_save) and the tables to ``path + ".npz"`` (no pickle)."""
+        if self.centroids is None or self.ids is None:
+            raise RuntimeError("nothing to save: train() and add rows first")
+        if self.extents:
+            el, ef, en = self.ext_list, self.ext_first, self.ext_nt
+            counts, tails, next_tile = self.counts, self.tails, self.next_tile
+            pos_of_id = self.pos_of_id
+        else:  # (a bulk-built index stays in its form; the file holds the equivalent extents)
+            lt = self.list_tiles.cpu().numpy().astype(np.int64)
+            el, ef, en = np.arange(self.nlist, dtype=np.int64), lt[:-1], np.diff(lt)
+            counts = np.bincount(self.lists_of_rows.cpu().numpy(), minlength=self.nlist).astype(np.int64)
+            tails, next_tile = ef * 32 + counts, int(lt[-1])
+            ids = self.ids.cpu().numpy()
+            pos_of_id = np.full(self.n, -1, np.int64)
+            live = np.nonzero(ids[: next_tile * 32] >= 0)[0]
+            pos_of_id[ids[live] - self.id_base] = live
+        self.index.save(path)
+        with open(path + ".npz.tmp", "wb") as f:
+            np.savez(f, centroids=self.centroids.cpu().numpy(), ext_list=el, ext_first=ef, ext_nt=en, counts=counts,
+                     tails=tails, ids=self.ids.cpu().numpy()[: next_tile * 32],
+                     lists_of_rows=self.lists_of_rows.cpu().numpy(), pos_of_id=pos_of_id,
+                     meta=np.array([self.dim, self.nlist, next_tile, self.id_base, self.n], np.int64),
+                     store_dtype=np.array(self.dtype), metric=np.array(self.metric))
+        os.replace(path + ".npz.tmp", path + ".npz")
+
+    @classmethod
+    def load(cls, path: str, device: int = 0) -> "IvfIndex":
+        import torch
+
+        z = np.load(path + ".npz", allow_pickle=False)
+        dim, nlist, next_tile, id_base, n = (int(v) for v in z["meta"])
+        self = cls.__new__(cls)
+        self.torch = torch
+        self.dim, self.nlist, self.dtype, self.metric = dim, nlist, str(z["store_dtype"]), str(z["metric"])
+        self.dev, self.device, self.dpad = torch.device("cuda", device), device, _round64(dim)
+        self.index = _native.NativeIndex.load(path, device=device, dim=dim, dtype=self.dtype, metric=self.metric,
+                                              no_shadows=True)
+        self.centroids = torch.from_numpy(z["centroids"]).to(self.dev).contiguous()
+        self.list_tiles, self.n, self.id_base = None, n, id_base
+        self.ext_list, self.ext_first, self.ext_nt = (z[k].astype(np.int64) for k in ("ext_list", "ext_first", "ext_nt"))
+        self.counts, self.tails = z["counts"].astype(np.int64), z["tails"].astype(np.int64)
+        self.ntiles = np.bincount(self.ext_list, weights=self.ext_nt, minlength=nlist).astype(np.int64)
+        self.caps, self.next_tile = self.ntiles * 32, next_tile
+        self.pos_of_id = z["pos_of_id"].astype(np.int64)
+        self.lists_of_rows = torch.from_numpy(z["lists_of_rows"].astype(np.int64)).to(self.dev)
+        self._ids_buf = torch.from_numpy(z["ids"].astype(np.int64)).to(self.dev)
+        self.ids = None
+        self.extents = True
+        self.ext_off = self.ext = self.list_ntiles = None
+        self.max_list_tiles = 0
+        self._sync_tables()
+        return self
 
     def close(self):
         self.index.close()

@@ -8,6 +8,10 @@ VectorStoreConfig :52, MonitorConfig :68, RAGConfig :85) so existing YAML
     configs are served by the same index (see storage.VectorStoreFactory);
   * VectorStoreConfig.index_params keys for the HIP index: dtype (bf16|f16|f32),
     device (int), capacity (rows), include_embeddings (bool), persist (bool);
+  * VectorStoreConfig.index_type "IVF_FLAT" (any letter case; single device, cosine / dot): IVF lists
+    beside the exact index, with index_params nlist (1024), nprobe (16), ivf_train_rows (64 * nlist: live
+    rows at which the lists are trained; exact search below) and ivf_seed (0).  None, "FLAT", "HNSW" and
+    any other value: the exact index;
   * EmbeddingConfig.provider also accepts "rocm" (the in-process embedder).
 Secrets (api_key, base_url) are masked in repr like utu/config/base_config.py:22-38.
 """

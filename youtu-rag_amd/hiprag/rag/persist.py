@@ -9,6 +9,8 @@ Replaces the persistence of the reference's stores -- Chroma's PersistentClient 
                                   a complete snapshot
   <collection>.g<g>.hri           the device index of generation g (hr_index_save: tiled rows
                                   + live bits, itself written tmp + fsync + rename)
+  <collection>.g<g>.hri.ivf.npz   index_type "IVF_FLAT" only: centroids and the list of every row
+                                  (ivf_store.py), written before the .hri
   <collection>.g<g>.rows.jsonl    header {"gen", "n_rows", ...} + one record per row (null =
                                   deleted)
   <collection>.g<g>.emb.npy       optional raw fp32 embeddings (keep_embeddings)
@@ -90,7 +92,7 @@ class Paths:
         # exactly this collection's names: a prefix match would also take a sibling collection's files
         # ("docs" vs "docs.gov")
         pat = re.compile(re.escape(os.path.basename(self.base))
-                         + r"\.(manifest\.json|g\d+\.(hri|rows\.jsonl|emb\.npy|journal)|hri|rows\.jsonl)(\.tmp)?")
+                         + r"\.(manifest\.json|g\d+\.(hri|hri\.ivf\.npz|rows\.jsonl|emb\.npy|journal)|hri|rows\.jsonl)(\.tmp)?")
         return [os.path.join(d, f) for f in os.listdir(d) if pat.fullmatch(f)]
 
 

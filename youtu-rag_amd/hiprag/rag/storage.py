@@ -44,6 +44,12 @@ Keyword search (opt-in, ``index_params.lexical: true``; single device): a BM25 f
 chunk contents row for row beside the dense index -- every add, delete and clear goes to both, a load rebuilds it
 from the stored contents (no file of its own) -- and ``keyword_search`` / ``keyword_search_batch`` answer through the
 same tables and the same ``filters`` bitmaps as ``search_batch``.  HybridRetriever fuses the two rankings.
+
+``index_type: "IVF_FLAT"`` (any letter case; single device, cosine / dot): the index is an ``IvfStoreIndex``
+(ivf_store.py) -- the same exact index plus an IVF replica that answers searches once ``ivf_train_rows`` live rows
+are stored (``index_params``: nlist, nprobe, ivf_train_rows = 64 nlist, ivf_seed).  It comes in through the
+``index_factory`` / ``index_loader`` seam; the tables, journal and snapshots are those of the exact store, plus one
+``.hri.ivf.npz`` per generation.  Any other ``index_type`` (None, "FLAT", "HNSW", ...) is the exact store.
 """
 from __future__ import annotations
 
@@ -65,6 +71,7 @@ from . import persist as P
 from .base import BaseVectorStore, Chunk
 from .lexical import MAX_K as _LEX_MAX_K, LexicalIndex
 from .config import VectorStoreConfig
+from .ivf_store import IvfStoreIndex, wants_ivf
 
 try:  # the per-hit result assembly in C (csrc/host/hostfast.c, built by csrc/Makefile); host-side only, same output
     from . import _hostfast
@@ -359,10 +366,21 @@ class HipVectorStore(BaseVectorStore):
         self.metric = _METRIC[config.distance_metric]
         if self.dtype not in _native.DTYPES:
             raise ValueError(f"unknown index dtype {self.dtype!r}")
-        self._factory = index_factory or (lambda dim: _native.NativeIndex(dim, self.dtype, self.metric,
-                                                                          devices=self.devices))
-        self._loader = index_loader or (lambda path, dim, dtype, metric: _native.NativeIndex.load(
-            path, devices=self.devices, dim=dim, dtype=dtype, metric=metric))
+        # index_type "IVF_FLAT": the exact index plus an IVF replica, through the same factory / loader seam
+        self.ivf = wants_ivf(config.index_type, self.metric, self.devices)
+        if self.ivf:
+            ivf_kw = dict(device=self.device, nlist=int(params.get("nlist", 1024)), nprobe=int(params.get("nprobe", 16)),
+                          train_rows=params.get("ivf_train_rows"), seed=int(params.get("ivf_seed", 0)))
+            default_factory = lambda dim: IvfStoreIndex(dim, self.dtype, self.metric, **ivf_kw)  # noqa: E731
+            default_loader = lambda path, dim, dtype, metric: IvfStoreIndex.load(  # noqa: E731
+                path, dim, dtype, metric, **ivf_kw)
+        else:
+            default_factory = lambda dim: _native.NativeIndex(dim, self.dtype, self.metric,  # noqa: E731
+                                                              devices=self.devices)
+            default_loader = lambda path, dim, dtype, metric: _native.NativeIndex.load(  # noqa: E731
+                path, devices=self.devices, dim=dim, dtype=dtype, metric=metric)
+        self._factory = index_factory or default_factory
+        self._loader = index_loader or default_loader
         self._batcher = _SearchBatcher(self, int(params.get("max_batch", 64)), int(params.get("search_depth", 2)))
         # unfiltered batches launched from the event loop through the asynchronous native entry point
         self.native_async = bool(params.get("native_async", True))
@@ -512,6 +530,14 @@ class HipVectorStore(BaseVectorStore):
                 if f.startswith(pt.base + f".g{old}.") or f in pt.legacy:
                     with contextlib.suppress(OSError):
                         os.remove(f)
+
+    def rebuild_ivf(self) -> None:
+        """Retrain the IVF replica of an ``index_type: "IVF_FLAT"`` store on the rows stored now and replace it
+        (nothing retrains by itself as a collection drifts)."""
+        with self._lock:
+            if self._index is None or not hasattr(self._index, "rebuild_ivf"):
+                raise ValueError('rebuild_ivf needs a store with index_type "IVF_FLAT" that holds rows')
+            self._index.rebuild_ivf(np.nonzero(self._live[: len(self._records)])[0])
 
     def _log(self, op: str, rows=None, records=None, vectors=None):
         """Persist one mutation: journal it, or mark the deferred block dirty."""
