@@ -139,6 +139,31 @@ int hr_index_search_collect(hr_index* h, int64_t ticket, float* scores_out, int6
  * queries need the exact fallback (collect then runs a corpus pass: call it off the event loop).  HR_E_BUSY
  * while another call holds the handle. */
 int hr_index_search_poll(hr_index* h, int64_t ticket, int* state_out);
+/* Collapsed search: the exact top-k DISTINCT groups of every query, each represented by its best row (Milvus'
+ * group-by search, Elasticsearch's collapse; replaces kb_file_search's over-fetch + host de-duplication by
+ * metadata.get("source", document_id), kb_search_toolkit.py:539-568, which cannot know whether another file sits
+ * just below its fetch window).
+ * The group column: one int32 id per row, -1 = no group.  hr_index_set_groups writes ids of rows [row0, row0 + n)
+ * from host memory; ids below -1 and rows at or beyond the index's row count: HR_E_INVALID.  The column is a device
+ * array owned by the handle, allocated by the first call (an index that never collapses pays nothing), grown by
+ * doubling with its contents kept, new entries -1; rows added later are -1 until set.  The library keeps
+ * largest id + 1 as the group count.  hr_index_save does not write the column: the caller derives it again.
+ * Semantics: let A be the live rows the mask allows with id >= 0, ordered as every search orders (canonical fp64
+ * score desc, row asc); walk A and keep a row only when its group has not been seen.  The first k kept rows are
+ * the result, scores cast to fp32 as hr_index_search does, slots after the last kept row -inf / -1.  With every
+ * row in a group of its own the result is hr_index_search's, bit for bit; with one group it is one row.
+ * Two stages: the exact search for `probe` rows (0 = the default: HR_MAX_K, 32 for k = 1; else k <= probe <=
+ * HR_MAX_K) collapsed on the device; a query whose probe came back full with fewer than k groups goes through an
+ * all-rows pass -- canonical score of every live, allowed row, atomic max per group, the exact record selector --
+ * one query at a time in a workspace of 12 bytes per index row + 32 bytes per group, with no n-row sort.
+ * 1 <= k <= HR_MAX_K, any B, every dtype and metric; a multi-device handle: HR_E_UNSUPPORTED; no group column:
+ * HR_E_INVALID.  The device form is ordered after the work queued on `stream` and returns with it idle. */
+int hr_index_set_groups(hr_index* h, int64_t row0, int64_t n, const int32_t* groups /* host */);
+int hr_index_search_collapsed(hr_index* h, const float* q, int B, int k, int probe, const uint64_t* row_mask,
+                              float* scores_out, int64_t* rows_out);
+int hr_index_search_collapsed_device(hr_index* h, const float* q_dev, int B, int k, int probe,
+                                     const uint64_t* row_mask_dev, float* scores_out_dev, int64_t* rows_out_dev,
+                                     void* stream);
 int hr_index_size(hr_index* h, int64_t* n_out, int64_t* n_live_out);
 /* Shape of a handle (e.g. one returned by hr_index_load): dim, storage dtype, metric, devices. */
 int hr_index_info(hr_index* h, int* dim_out, int* dtype_out, int* metric_out, int* n_dev_out);

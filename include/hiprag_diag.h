@@ -59,6 +59,14 @@ int hr_index_wide_launches(hr_index* h, int64_t* out);
 /* Diagnostics: 256-query FILTER launches issued so far (graph replays not counted). */
 int hr_index_q256_launches(hr_index* h, int64_t* out);
 
+/* Diagnostics of the collapsed search (hr_index_search_collapsed): cumulative queries answered from the probe
+ * (out[0]) and by the all-rows pass (out[1]).  set_collapse_timing(h, 1) records HIP events around the stages of
+ * every collapsed call; collapse_last_ms then reports the most recent call's probe search, prefix kernel and
+ * all-rows stage (ms; the last one covers all its incomplete queries, host waits between them included). */
+int hr_index_collapse_stats(hr_index* h, int64_t out[2]);
+int hr_index_set_collapse_timing(hr_index* h, int on);
+int hr_index_collapse_last_ms(hr_index* h, double out[3]);
+
 /* Diagnostics of the pipelined search: out[0] = caller host time per submit (us), out[1] = host time
  * per batch of the busiest shard thread (us), out[2] = batches submitted. */
 int hr_index_host_us(hr_index* h, double* out);

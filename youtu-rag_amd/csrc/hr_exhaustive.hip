@@ -96,6 +96,20 @@ int build_tile_list(const uint32_t* live, const uint32_t* mask, int64_t n_tiles,
                : HR_E_HIP;
 }
 
+int exact_all_keys(const uint8_t* rows, int dtype, int S, int dpad, const float* qv, int metric, double qn2,
+                   const uint32_t* live, const uint32_t* mask, int64_t n, uint64_t* k_in, uint32_t* v_in,
+                   hipStream_t st) {
+    if (n <= 0) return HR_OK;
+    const dim3 grid((unsigned)((n + 3) / 4));
+    switch (dtype) {
+        case HR_F32: hipLaunchKernelGGL(k_exact_all<F32>, grid, dim3(256), 0, st, rows, S, dpad, qv, metric, qn2, live, mask, n, k_in, v_in); break;
+        case HR_BF16: hipLaunchKernelGGL(k_exact_all<BF16>, grid, dim3(256), 0, st, rows, S, dpad, qv, metric, qn2, live, mask, n, k_in, v_in); break;
+        case HR_F16: hipLaunchKernelGGL(k_exact_all<F16>, grid, dim3(256), 0, st, rows, S, dpad, qv, metric, qn2, live, mask, n, k_in, v_in); break;
+        default: return HR_E_INVALID;
+    }
+    return hipGetLastError() == hipSuccess ? HR_OK : HR_E_HIP;
+}
+
 // scratch layout: keys_in, keys_out (8n each), vals_in, vals_out (4n each), radix-sort temp
 size_t exhaustive_scratch_bytes(int64_t n) {
     size_t tmp = 0;
@@ -127,14 +141,7 @@ int exhaustive_topm(const uint8_t* rows, int dtype, int S, int dpad, const float
     uint8_t* tmp = p + 2 * up(8 * (size_t)n) + 2 * up(4 * (size_t)n);
     if (scratch_bytes < exhaustive_scratch_bytes(n)) return HR_E_INVALID;
     size_t tmp_bytes = scratch_bytes - (size_t)(tmp - p);
-    const dim3 grid((unsigned)((n + 3) / 4));
-    switch (dtype) {
-        case HR_F32: hipLaunchKernelGGL(k_exact_all<F32>, grid, dim3(256), 0, st, rows, S, dpad, qv, metric, qn2, live, mask, n, k_in, v_in); break;
-        case HR_BF16: hipLaunchKernelGGL(k_exact_all<BF16>, grid, dim3(256), 0, st, rows, S, dpad, qv, metric, qn2, live, mask, n, k_in, v_in); break;
-        case HR_F16: hipLaunchKernelGGL(k_exact_all<F16>, grid, dim3(256), 0, st, rows, S, dpad, qv, metric, qn2, live, mask, n, k_in, v_in); break;
-        default: return HR_E_INVALID;
-    }
-    if (hipGetLastError() != hipSuccess) return HR_E_HIP;
+    if (int rc = exact_all_keys(rows, dtype, S, dpad, qv, metric, qn2, live, mask, n, k_in, v_in, st)) return rc;
     if (rocprim::radix_sort_pairs_desc(tmp, tmp_bytes, k_in, k_out, v_in, v_out, (size_t)n, 0, 64, st) != hipSuccess)
         return HR_E_HIP;
     hipLaunchKernelGGL(k_take, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, k_out, v_out, n, m, row_offset,

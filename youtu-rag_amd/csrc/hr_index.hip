@@ -1804,6 +1804,12 @@ extern "C" int hr_index_search_device(hr_index* h, const float* q_dev, int B, in
     return search_device_impl(h, q_dev, B, k, row_mask_dev, scores_out_dev, rows_out_dev, st);
 }
 
+int index_search_locked(hr_index* h, const float* q_dev, int B, int k, const uint64_t* mask_dev, float* s_out,
+                        int64_t* r_out, hipStream_t st) {
+    if (int rc = persist_close(h)) return rc;  // a running persistent FILTER leaves the CUs to this search
+    return search_device_impl(h, q_dev, B, k, mask_dev, s_out, r_out, st);
+}
+
 // Pipelined search (include/hiprag.h): a group handle keeps two batches in flight, every shard
 // submitted by its own host thread (hr_group.hip); a single-device handle runs the batch at once
 // (ticket 0; ShardedSearch pipelines single-device shards from Python).
@@ -2021,11 +2027,9 @@ extern "C" int hr_index_host_us(hr_index* h, double* out) {
     return HR_OK;
 }
 
-// Exact top-m of every query over the whole shard into device records out_dev[B][m] (local row + row_offset;
-// -inf / -1 padding past the live, allowed rows): canonical fp64 score of every row + stable radix sort, the same
-// arithmetic and (score desc, row asc) order as the scan path.  One corpus pass and one n-row sort per query.
-static int index_exact_dev(hr_index* h, const float* q_dev, int B, int m, const uint64_t* mask_dev, int64_t row_offset,
-                           Cand* out_dev, hipStream_t st) {
+// the all-rows exact pass's query prep (hr_internal.hpp); the queries land in the synchronous workspace's q32
+int index_prep_exact(hr_index* h, const float* q_dev, int B, hipStream_t st, const float** q32_out,
+                     std::vector<double>* qerr_out) {
     Scratch& sc = h->scr[kSyncSet];
     const int QB = (B + 31) / 32, Bp = QB * 32;
     HIP_TRY(sc.q32.ensure((size_t)Bp * h->dpad * 4));
@@ -2040,12 +2044,25 @@ static int index_exact_dev(hr_index* h, const float* q_dev, int B, int m, const 
                            QB, h->metric, sc.q32.as<float>(), sc.qfrag.as<uint16_t>(), sc.qerr.as<double>(), nullptr, 1,
                            nullptr, nullptr, nullptr);
     HIP_TRY(hipGetLastError());
-    std::vector<double> qerr((size_t)Bp * 4);
+    std::vector<double>& qerr = *qerr_out;
+    qerr.assign((size_t)Bp * 4, 0.0);
     HIP_TRY(hipMemcpyAsync(qerr.data(), sc.qerr.p, qerr.size() * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
+    *q32_out = sc.q32.as<float>();
+    return HR_OK;
+}
+
+// Exact top-m of every query over the whole shard into device records out_dev[B][m] (local row + row_offset;
+// -inf / -1 padding past the live, allowed rows): canonical fp64 score of every row + stable radix sort, the same
+// arithmetic and (score desc, row asc) order as the scan path.  One corpus pass and one n-row sort per query.
+static int index_exact_dev(hr_index* h, const float* q_dev, int B, int m, const uint64_t* mask_dev, int64_t row_offset,
+                           Cand* out_dev, hipStream_t st) {
+    const float* q32 = nullptr;
+    std::vector<double> qerr;
+    if (int rc = index_prep_exact(h, q_dev, B, st, &q32, &qerr)) return rc;
     if (h->n > 0) HIP_TRY(h->exh.ensure(exhaustive_scratch_bytes(h->n)));
     for (int b = 0; b < B; ++b) {
-        if (int rc = exhaustive_topm(h->rows, h->dtype, h->S, h->dpad, sc.q32.as<float>() + (int64_t)b * h->dpad,
+        if (int rc = exhaustive_topm(h->rows, h->dtype, h->S, h->dpad, q32 + (int64_t)b * h->dpad,
                                      h->metric, qerr[4 * (size_t)b + 2], h->live, (const uint32_t*)mask_dev, h->n,
                                      row_offset, m, out_dev + (int64_t)b * m, h->exh.p, h->exh.bytes, st, h->stripe_G,
                                      h->stripe_s))
@@ -2529,6 +2546,7 @@ extern "C" void hr_index_destroy(hr_index* h) {
     if (h->live) (void)hipFree(h->live);
     if (h->xnorm) (void)hipFree(h->xnorm);
     if (h->norm_bits) (void)hipFree(h->norm_bits);
+    collapse_free(h);
     (void)hipDeviceSynchronize();  // pipelined batches may still run on caller streams
     for (auto& g : h->sync_graphs)
         if (g.exec) (void)hipGraphExecDestroy(g.exec);

@@ -64,6 +64,11 @@ struct DevBuf {
 };
 
 namespace hr {  // hr_exhaustive.hip
+// the exhaustive pass's first half on its own (k_exact_all): keys[r] = d2key(canonical fp64 score of row r), 0 for
+// a deleted or masked-out row, vals[r] = r, for r in [0, n); the collapsed search's stage 2 reduces them by group
+int exact_all_keys(const uint8_t* rows, int dtype, int S, int dpad, const float* qv, int metric, double qn2,
+                   const uint32_t* live, const uint32_t* mask, int64_t n, uint64_t* keys, uint32_t* vals,
+                   hipStream_t st);
 size_t exhaustive_scratch_bytes(int64_t n);
 int exhaustive_topm(const uint8_t* rows, int dtype, int S, int dpad, const float* qv, int metric, double qn2,
                     const uint32_t* live,
@@ -262,6 +267,18 @@ struct hr_index {
     // hr_index_set_cu_mask: the CUs this index's own streams may use (empty: all).  Every internal stream is then
     // created with hipExtStreamCreateWithCUMask and the launch grids are sized for popcount(mask) CUs
     std::vector<uint32_t> cu_mask;
+    // ---- collapsed search (hr_collapse.hip): the group column -- one int32 id per row, -1 = no group -- allocated by
+    // the first hr_index_set_groups and grown by doubling on its own (index_grow never sees it): entries
+    // [0, groups_cap) exist, rows at or beyond groups_cap count as -1.  n_groups = largest id set so far + 1.
+    int32_t* groups = nullptr;
+    int64_t groups_cap = 0;
+    int64_t n_groups = 0;
+    DevBuf col_q, col_mask, col_s, col_r, col_flag, col_out;  // host queries / mask, probe results, flags, host results
+    DevBuf col_keys, col_g, col_top;  // stage 2: score keys + rows of one query (12 n bytes), group tables, top-k
+    int64_t n_collapse_probe = 0, n_collapse_all = 0;  // queries answered from the probe / by the all-rows pass
+    bool collapse_timing = false;     // hr_index_set_collapse_timing: HIP events around the stages of every call
+    hipEvent_t col_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    double col_ms[3] = {0.0, 0.0, 0.0};  // probe search, prefix kernel, stage 2 of the most recent timed call
 };
 
 // an internal stream of h: on h's CU mask when one is set (priority is then not available), else high priority or
@@ -314,6 +331,15 @@ int index_shard_collect(hr_index* h, const float* q_dev, int B, const double* kt
 int index_exact_all(hr_index* h, const float* q_dev, int B, int m, const uint64_t* mask_dev, Cand* out_host,
                     hipStream_t st);
 int index_host_tile_list(hr_index* h, const uint32_t* mask_words, hipStream_t st);
+// collapsed search (hr_collapse.hip) over the single-shard search; the caller holds h->mu with h's device current.
+// index_search_locked: hr_index_search_device without the lock (the full exact search, fallback included);
+// index_prep_exact: the canonical fp32 queries of the all-rows exact pass (dpad floats each, at *q32_out) and
+// their host-side terms (qerr_out[4 b + 2] = |q_b|^2); synchronises st.  collapse_free: hr_index_destroy's part.
+int index_search_locked(hr_index* h, const float* q_dev, int B, int k, const uint64_t* mask_dev, float* s_out,
+                        int64_t* r_out, hipStream_t st);
+int index_prep_exact(hr_index* h, const float* q_dev, int B, hipStream_t st, const float** q32_out,
+                     std::vector<double>* qerr_out);
+void collapse_free(hr_index* h);
 int launch_merge(int device, const Cand* cand, const double* bounds, int G, int B, int kc, int k, float* s_out,
                  int64_t* r_out, double* kth_out, int32_t* fail_out, hipStream_t st, int64_t cstride = 0,
                  int64_t bstride = 0);

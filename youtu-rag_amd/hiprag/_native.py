@@ -56,7 +56,8 @@ EXPORTS = [
     "hr_lex_pack", "hr_lex_create", "hr_lex_destroy", "hr_lex_add", "hr_lex_remove", "hr_lex_size", "hr_lex_stats",
     "hr_lex_df", "hr_lex_search", "hr_lex_last_ms", "hr_index_set_shadow8", "hr_index_debug_approx8",
     "hr_index_shadow8_stats", "hr_index_create_ex", "hr_index_load_ex", "hr_index_copy_rows", "hr_ivf_search_ext",
-    "hr_ivf_position_mask",
+    "hr_ivf_position_mask", "hr_index_set_groups", "hr_index_search_collapsed", "hr_index_search_collapsed_device",
+    "hr_index_collapse_stats", "hr_index_set_collapse_timing", "hr_index_collapse_last_ms",
 ]
 
 _lib = None
@@ -199,6 +200,12 @@ def load_library(path: str | None = None):
             "hr_lex_df": [vp, vp, i64, vp],
             "hr_lex_search": [vp, vp, vp, i32, i32, ctypes.c_double, ctypes.c_double, vp, vp, vp],
             "hr_lex_last_ms": [vp, vp],
+            "hr_index_set_groups": [vp, i64, i64, vp],
+            "hr_index_search_collapsed": [vp, vp, i32, i32, i32, vp, vp, vp],
+            "hr_index_search_collapsed_device": [vp, vp, i32, i32, i32, vp, vp, vp, vp],
+            "hr_index_collapse_stats": [vp, vp],
+            "hr_index_set_collapse_timing": [vp, i32],
+            "hr_index_collapse_last_ms": [vp, vp],
         }
         for name, args in sig.items():
             if p != (path or LIB_PATH) and not hasattr(L, name):
@@ -376,6 +383,59 @@ class NativeIndex:
                                  f"(needs {(n_rows + 63) // 64})")
         _check(self.lib.hr_index_search(self._h, _ptr(q), B, int(k), _ptr(m), _ptr(s), _ptr(r)))
         return s, r
+
+    def _mask_words(self, mask):
+        if mask is None:
+            return None
+        m = np.ascontiguousarray(mask, np.uint64).reshape(-1)
+        n_rows = self.size()[0]
+        if len(m) * 64 < n_rows:  # the library reads one bit per index row
+            raise ValueError(f"row mask has {len(m)} words, the index {n_rows} rows (needs {(n_rows + 63) // 64})")
+        return m
+
+    # -- collapsed search (hr_collapse.hip): the exact top-k distinct groups, each by its best row
+    def set_groups(self, row0: int, groups) -> None:
+        """Group ids (int32, -1 = none) of rows [row0, row0 + len(groups)) (hr_index_set_groups)."""
+        g = np.ascontiguousarray(np.asarray(groups, np.int32).reshape(-1))
+        _check(self.lib.hr_index_set_groups(self._h, int(row0), len(g), _ptr(g)))
+
+    def search_collapsed(self, q: np.ndarray, k: int, mask: np.ndarray | None = None,
+                         probe: int = 0) -> tuple[np.ndarray, np.ndarray]:
+        """search() with one hit per group: the best row of each of the k best groups, exactly
+        (hr_index_search_collapsed).  ``probe``: rows the first stage fetches (0 = the library's default)."""
+        q = np.ascontiguousarray(q, np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.shape[1] != self.dim:
+            raise ValueError(f"query dim {q.shape[1]} != index dim {self.dim}")
+        B = q.shape[0]
+        s = np.empty((B, k), np.float32)
+        r = np.empty((B, k), np.int64)
+        m = self._mask_words(mask)
+        _check(self.lib.hr_index_search_collapsed(self._h, _ptr(q), B, int(k), int(probe), _ptr(m), _ptr(s), _ptr(r)))
+        return s, r
+
+    def search_collapsed_device(self, q_ptr: int, B: int, k: int, scores_ptr: int, rows_ptr: int, mask_ptr: int = 0,
+                                probe: int = 0, stream: int = 0) -> None:
+        _check(self.lib.hr_index_search_collapsed_device(self._h, ctypes.c_void_p(q_ptr), int(B), int(k), int(probe),
+                                                         ctypes.c_void_p(mask_ptr or None),
+                                                         ctypes.c_void_p(scores_ptr), ctypes.c_void_p(rows_ptr),
+                                                         ctypes.c_void_p(stream or None)))
+
+    def collapse_stats(self) -> dict:
+        """Cumulative collapsed queries answered from the probe / by the all-rows pass."""
+        out = (ctypes.c_int64 * 2)()
+        _check(self.lib.hr_index_collapse_stats(self._h, out))
+        return {"probe": int(out[0]), "all_rows": int(out[1])}
+
+    def set_collapse_timing(self, on: bool) -> None:
+        _check(self.lib.hr_index_set_collapse_timing(self._h, int(bool(on))))
+
+    def collapse_last_ms(self) -> dict:
+        """HIP-event times of the most recent timed collapsed call (set_collapse_timing)."""
+        out = (ctypes.c_double * 3)()
+        _check(self.lib.hr_index_collapse_last_ms(self._h, out))
+        return {"probe_ms": out[0], "prefix_ms": out[1], "all_rows_ms": out[2]}
 
     def search_device(self, q_ptr: int, B: int, k: int, scores_ptr: int, rows_ptr: int, mask_ptr: int = 0,
                       stream: int = 0) -> None:

@@ -199,6 +199,16 @@ class IvfStoreIndex:
             del keep
         return host[..., 0].astype(np.float32), host.view(np.int64)[..., 1].copy()
 
+    # collapsed search (one hit per group) is always exact: the exact index holds the group column and answers
+    def set_groups(self, row0: int, groups) -> None:
+        self.exact.set_groups(row0, groups)
+
+    def search_collapsed(self, q: np.ndarray, k: int, mask: np.ndarray | None = None, probe: int = 0):
+        return self.exact.search_collapsed(q, k, mask, probe)
+
+    def collapse_stats(self) -> dict:
+        return self.exact.collapse_stats()
+
     # ---------------------------------------------------------------- persistence
     def save(self, path: str) -> None:
         """The exact index to ``path`` as ever, and ``path + ".ivf.npz"``: centroids, nlist, the seed, the list of

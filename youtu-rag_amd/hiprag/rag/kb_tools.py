@@ -19,6 +19,9 @@ Reference quirks kept: ``file_search_top_k`` reads the same "top_k" key as conte
 ``kb_rerank`` passes ``top_n=`` to ``rerank()`` (:391-393), which the rerankers do not accept, so the
 tool answers with its error JSON; an unknown kb_id fails before the not-found check (:46) with the
 same error shape.
+One addition, off by default: ``config["collapse_files"]`` makes ``kb_file_search`` ask the store for distinct files
+(a collapsed search by ``source``) instead of de-duplicating an over-fetch on the host, which returns
+fewer than ``top_k`` files whenever one file owns most of the fetched rows (kb_search_toolkit.py:539-568).
 """
 from __future__ import annotations
 
@@ -88,10 +91,13 @@ class BaseRAGToolkit:
     def _get_or_create_vector_store(self, collection_name: str, persist_directory: str):
         if collection_name not in self._vector_store_cache:
             vs = self.vector_store_base_config
+            index_params = dict(vs.get("index_params") or {})
+            if self.config.config.get("collapse_files", False):  # kb_file_search collapses by file name
+                index_params.setdefault("collapse_field", "source")
             cfg = VectorStoreConfig(backend=vs.get("backend", "chroma"), persist_directory=persist_directory,
                                     collection_name=collection_name,
                                     distance_metric=vs.get("distance_metric", "cosine"),
-                                    index_params=vs.get("index_params") or {})
+                                    index_params=index_params)
             if self._store_factory is not None:
                 self._vector_store_cache[collection_name] = self._store_factory(cfg)
             else:
@@ -128,6 +134,8 @@ class KBSearchToolkit(BaseRAGToolkit):
         self.file_search_top_k = c.get("top_k", 15)
         self.recall_multiplier = c.get("recall_multiplier", 3)
         self.reranker_config = c.get("reranker", {})
+        # kb_file_search through the store's collapsed search: the fetched rows are distinct files already
+        self.collapse_files = bool(c.get("collapse_files", False))
         self.reranker = self._init_reranker()
 
     def _init_reranker(self):
@@ -233,8 +241,13 @@ class KBSearchToolkit(BaseRAGToolkit):
             base = self._build_metadata_filters(metadata_filters)
             summary_only = {"index_type": {"$eq": "index_summary"}}
             filters = {"$and": [base, summary_only]} if base else summary_only
-            retriever = await self._create_retriever(kb_id, retrieval_top_k)
-            results = await retriever.retrieve(query=query, filters=filters)
+            if self.collapse_files:  # one row per file from the store (at most HR_MAX_K files): the loop below keeps all
+                retrieval_top_k = min(retrieval_top_k, 128)
+                retriever = await self._create_retriever(kb_id, retrieval_top_k)
+                results = await retriever.retrieve(query=query, filters=filters, collapse=True)
+            else:
+                retriever = await self._create_retriever(kb_id, retrieval_top_k)
+                results = await retriever.retrieve(query=query, filters=filters)
             files: dict[str, dict] = {}
             hidden = {"index_type", "chunk_index", "_derived_files_etags"}
             for r in results:  # one entry per file: its best summary vector

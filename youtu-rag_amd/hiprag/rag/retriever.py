@@ -9,6 +9,9 @@ VectorRetriever keeps the reference's semantics exactly
   * ranks are the 1-based positions BEFORE threshold filtering (:72), and a
     threshold <= 0 disables filtering (:71);
   * optional rerank, then ``[:top_k]`` (:75-80).
+``collapse=True`` in the kwargs (no counterpart in the reference) asks the store for one hit per group -- the best chunk
+of each of the best documents (HipVectorStore, ``collapse_field``); threshold, ranks and the ``2*top_k`` fetch under a
+reranker apply to the collapsed list as to the plain one.
 BatchedVectorRetriever overrides batch_retrieve (the reference's loop at :95-98)
 with one query-embedding batch and one GPU search launch for the whole batch,
 producing the same per-query results.
@@ -270,11 +273,13 @@ class VectorRetriever(BaseRetriever):
     async def retrieve(self, query: str, top_k: int | None = None, **kwargs) -> list[RetrievalResult]:
         top_k = top_k or self.config.top_k
         threshold = kwargs.get("similarity_threshold", self.config.similarity_threshold)
-        if self._fused is not None and not kwargs.get("filters") and self.reranker is None:
+        collapse = bool(kwargs.get("collapse", False))
+        if self._fused is not None and not kwargs.get("filters") and self.reranker is None and not collapse:
             return await self._fused.submit(query, top_k, threshold)
         qv = await self.embedder.embed_query(query)
+        extra = {"collapse": True} if collapse else {}  # (off: the reference's call, for any store)
         hits = await self.vector_store.search(query_embedding=qv, top_k=top_k * 2 if self.reranker else top_k,
-                                              filters=kwargs.get("filters"))
+                                              filters=kwargs.get("filters"), **extra)
         return await self._finish(query, self._to_results(hits, threshold), top_k)
 
     async def batch_retrieve(self, queries: list[str], top_k: int | None = None, **kwargs
@@ -297,7 +302,8 @@ class BatchedVectorRetriever(VectorRetriever):
         threshold = kwargs.get("similarity_threshold", self.config.similarity_threshold)
         embed_many = getattr(self.embedder, "embed_queries", None)
         qvs = await embed_many(queries) if embed_many else [await self.embedder.embed_query(q) for q in queries]
-        hits = search_batch(qvs, top_k * 2 if self.reranker else top_k, kwargs.get("filters"))
+        extra = {"collapse": True} if kwargs.get("collapse", False) else {}
+        hits = search_batch(qvs, top_k * 2 if self.reranker else top_k, kwargs.get("filters"), **extra)
         results = [self._to_results(h, threshold) for h in hits]
         rerank_batch = getattr(self.reranker, "rerank_batch", None)
         if rerank_batch is not None:  # one set of cross-encoder batches for every query's pairs
@@ -373,6 +379,9 @@ class HybridRetriever(BaseRetriever):
         keyword_search = self._keyword_search()
         if keyword_search is None:
             return await self.vector_retriever.batch_retrieve(queries=queries, top_k=top_k, **kwargs)
+        if kwargs.get("collapse", False):
+            raise ValueError("HybridRetriever does not fuse collapsed lists: collapse=True needs a store without an "
+                             "active keyword search, or VectorRetriever")
         if not queries:
             return []
         top_k = top_k or self.config.top_k

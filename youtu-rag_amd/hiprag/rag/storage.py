@@ -45,6 +45,14 @@ chunk contents row for row beside the dense index -- every add, delete and clear
 from the stored contents (no file of its own) -- and ``keyword_search`` / ``keyword_search_batch`` answer through the
 same tables and the same ``filters`` bitmaps as ``search_batch``.  HybridRetriever fuses the two rankings.
 
+Collapsed search (``search(..., collapse=True)`` / ``search_batch(..., collapse=True)``; single device): one hit per
+group -- the best chunk of each of the ``top_k`` best groups, exactly (hr_index_search_collapsed).  The
+group of a row is its ``document_id`` (``index_params.collapse_field``, the default) or the value of the metadata key
+that field names; a row without that key groups by its document_id, as kb_file_search's
+``metadata.get("source", document_id)`` does (kb_search_toolkit.py:547).  The value -> id dictionary (keyed on
+(type, value): 1, 1.0 and True stay apart) and a host int32 column are built at the first collapsed search and
+extended by every add; nothing of them is persisted.
+
 ``index_type: "IVF_FLAT"`` (any letter case; single device, cosine / dot): the index is an ``IvfStoreIndex``
 (ivf_store.py) -- the same exact index plus an IVF replica that answers searches once ``ivf_train_rows`` live rows
 are stored (``index_params``: nlist, nprobe, ivf_train_rows = 64 nlist, ivf_seed).  It comes in through the
@@ -170,7 +178,7 @@ class _SearchBatcher:
     as a count on an eventfd the loop watches (written by a host function behind the batch's results), so
     no Python thread takes part -- no GIL hand-off between a worker and the loop per launch.  Filtered
     batches, multi-device handles, and launches that find the handle or the store busy run the blocking
-    search in a worker thread (``asyncio.to_thread``; ctypes drops the GIL)."""
+    search in a worker thread (``asyncio.to_thread``; ctypes drops the GIL), and so do collapsed batches."""
 
     def __init__(self, store: "HipVectorStore", max_batch: int, depth: int = 2):
         self.store, self.max_batch, self.depth = store, max(1, int(max_batch)), max(1, int(depth))
@@ -184,7 +192,7 @@ class _SearchBatcher:
         self._drain_loop = None   # the loop the running drain belongs to
         self._inflight: dict = {}  # the running drain's launches: awaitable -> (batch, prep, native info or None)
 
-    def submit(self, q: np.ndarray, top_k: int, filters) -> asyncio.Future:
+    def submit(self, q: np.ndarray, top_k: int, filters, collapse: bool = False) -> asyncio.Future:
         """Queue one query; the future resolves to its (Chunk, score) list.  A plain call, not a coroutine: the
         caller's own coroutine awaits the future, so a query in flight holds one coroutine frame fewer for the
         cycle collector to walk and promote (the store's event loop is collector-bound under load)."""
@@ -195,7 +203,9 @@ class _SearchBatcher:
         if self._drain_loop is not None and self._drain_loop is not loop and self._drain_loop.is_closed():
             self._recover_from_closed_loop(loop)
         fut = loop.create_future()
-        self.pending.append((q, int(top_k), filters, _filter_key(filters), fut))
+        # collapsed and plain queries never share a launch: the flag is part of the group key
+        key = _filter_key(filters)
+        self.pending.append((q, int(top_k), filters, "collapse\0" + key if collapse else key, fut, bool(collapse)))
         if not self.running:
             self.running, self._drain_loop = True, loop
             # start draining on the next loop iteration: every task that is ready now enqueues first
@@ -294,7 +304,7 @@ class _SearchBatcher:
                         qs = np.stack([e[0] for e in batch])
                         k = max(e[1] for e in batch)
                         self.launches += 1
-                        prep = self.store._prep_search(qs, k, batch[0][2])
+                        prep = self.store._prep_search(qs, k, batch[0][2], collapse=batch[0][5])
                         aw, info = self._launch(loop, prep)
                     except Exception as exc:  # noqa: BLE001 -- this batch's waiters see the failure
                         self._fail(batch, exc)
@@ -355,6 +365,8 @@ class HipVectorStore(BaseVectorStore):
         self._lex_factory = lexical_factory or (lambda: LexicalIndex(
             self.device, float(params.get("bm25_k1", 1.2)), float(params.get("bm25_b", 0.75))))
         self.capacity = int(params.get("capacity", 0))
+        # collapsed search: what a row groups by -- its document_id, or this metadata key (document_id where absent)
+        self.collapse_field = str(params.get("collapse_field", "document_id"))
         self.include_embeddings = bool(params.get("include_embeddings", False))
         self.keep_embeddings = bool(params.get("keep_embeddings", False))
         # returned Chunks with atomic-valued metadata left off the cycle collector (faster under heavy load; a cycle
@@ -414,6 +426,11 @@ class HipVectorStore(BaseVectorStore):
         self._live = np.zeros(0, bool)
         self._raw = None  # keep_embeddings: (capacity, dim) fp32 host copy
         self._defer, self._dirty = 0, False
+        # collapsed search, built at the first one (_ensure_groups): (type, value) -> group id, the host column of
+        # group ids (one int32 per row, -1 for a dead row) and how many of its rows the index holds already
+        self._group_ids: dict | None = None
+        self._group_col = np.zeros(0, np.int32)
+        self._group_rows = self._group_sent = 0
 
     # ---------------------------------------------------------------- persistence
     def _load_if_present(self):
@@ -595,6 +612,8 @@ class HipVectorStore(BaseVectorStore):
                 self._doc_rows.setdefault(rec["document_id"], array("q")).append(first + i)
         self._cols.append([(rec or {}).get("metadata", {}) for rec in records])
         self._lex_append(first, [None if rec is None else rec["content"] for rec in records])
+        if self._group_ids is not None:
+            self._extend_groups(len(self._records))
         n = len(self._records)
         if len(self._live) < n:
             live = np.zeros(max(n, 2 * len(self._live), 1024), bool)
@@ -609,6 +628,45 @@ class HipVectorStore(BaseVectorStore):
                 self._raw = raw
             if vectors is not None:
                 self._raw[first:n] = vectors
+
+    def _extend_groups(self, n: int):
+        """Group ids of rows [_group_rows, n) into the host column (store lock held)."""
+        first = self._group_rows
+        if n <= first:
+            return
+        if len(self._group_col) < n:
+            col = np.full(max(n, 2 * len(self._group_col), 1024), -1, np.int32)
+            col[:first] = self._group_col[:first]
+            self._group_col = col
+        ids, field, by_doc = self._group_ids, self.collapse_field, self.collapse_field == "document_id"
+        for row in range(first, n):
+            rec = self._records[row]
+            if rec is None:
+                self._group_col[row] = -1
+                continue
+            v = rec[1] if by_doc else (self._metas[row] or {}).get(field, rec[1])
+            try:
+                key = (type(v), v)
+                g = ids.get(key)
+            except TypeError:  # an unhashable value (a list): by its text
+                key = (type(v), repr(v))
+                g = ids.get(key)
+            if g is None:
+                g = ids[key] = len(ids)
+            self._group_col[row] = g
+        self._group_rows = n
+
+    def _ensure_groups(self):
+        """The group column current on the host and on the device (store lock held, an index present): built from the
+        host tables at the first collapsed search -- after a reload too, nothing of it is persisted -- then extended by
+        _append_tables; the rows the index has not seen yet go up here."""
+        n = len(self._records)
+        if self._group_ids is None:
+            self._group_ids, self._group_rows, self._group_sent = {}, 0, 0
+        self._extend_groups(n)
+        if self._group_sent < n:
+            self._index.set_groups(self._group_sent, self._group_col[self._group_sent:n])
+            self._group_sent = n
 
     def _lex_append(self, first: int, contents: list):
         """The same rows into the lexical index (None: a dead row -- it takes its row number and no terms)."""
@@ -795,10 +853,11 @@ class HipVectorStore(BaseVectorStore):
             return self._raw[np.asarray(rows, np.int64)]
         return self._index.get_rows(rows)
 
-    def search_batch(self, query_embeddings, top_k: int = 5, filters: dict[str, Any] | None = None
-                     ) -> list[list[tuple[Chunk, float]]]:
-        """Batched search: one GPU launch for all queries (BatchedVectorRetriever, the micro-batcher)."""
-        prep = self._prep_search(query_embeddings, top_k, filters)
+    def search_batch(self, query_embeddings, top_k: int = 5, filters: dict[str, Any] | None = None, *,
+                     collapse: bool = False) -> list[list[tuple[Chunk, float]]]:
+        """Batched search: one GPU launch for all queries (BatchedVectorRetriever, the micro-batcher).
+        ``collapse=True``: one hit per group (collapse_field), the best chunk of each of the top_k best groups."""
+        prep = self._prep_search(query_embeddings, top_k, filters, collapse=collapse)
         return self._assemble(prep, self._run_search(prep))
 
     def keyword_search_batch(self, queries: list[str], top_k: int = 5, filters: dict[str, Any] | None = None
@@ -828,26 +887,40 @@ class HipVectorStore(BaseVectorStore):
     # search_batch in three steps, so the micro-batcher can run only the middle one in a worker thread
     # (it holds the GIL for little but the ctypes call; a worker doing the Python parts was starved by
     # a busy event loop) and assemble on the event-loop thread while the next launch runs
-    def _prep_search(self, query_embeddings, top_k: int, filters):
+    def _prep_search(self, query_embeddings, top_k: int, filters, collapse: bool = False):
         q = np.asarray(query_embeddings, dtype=np.float32)
         if q.ndim == 1:
             q = q[None, :]
         dim = self.dim
         if dim is not None and q.shape[1] != dim:
             raise ValueError(f"query dim {q.shape[1]} != collection dim {dim}")
-        return (q, int(top_k), filters)
+        return (q, int(top_k), filters, True) if collapse else (q, int(top_k), filters)
+
+    def _run_collapsed(self, q, top_k: int, filters, n_live: int):
+        """The collapsed native search (store lock held, rows present)."""
+        if top_k > _native.HR_MAX_K:
+            raise ValueError(f"a collapsed search returns at most {_native.HR_MAX_K} groups (top_k = {top_k})")
+        idx = self._index
+        if len(getattr(idx, "devices", (0,))) > 1:
+            raise ValueError("a collapsed search needs a single-device store")
+        if not hasattr(idx, "search_collapsed") or not hasattr(idx, "set_groups"):
+            raise NotImplementedError(f"{type(idx).__name__} has no collapsed search")
+        self._ensure_groups()  # under the same lock hold as the search
+        return idx.search_collapsed(q, min(top_k, n_live), self.filter_bitmap(filters))
 
     def _run_search(self, prep):
         """The native search, under the store lock.  Everything that depends on the collection's
         current state -- the live row count, the filter bitmap (sized to the index's rows NOW, not when
         the query was queued: rows added in between would otherwise make the bitmap too short), the
         tables the rows resolve through -- is taken here, under the same lock as the search."""
-        q, top_k, filters = prep
+        q, top_k, filters = prep[:3]
         with self._lock:  # ordered against mutations
             tables = (self._records, self._metas, self._epoch)
             n_live = self.count_sync()
             if self._index is None or n_live == 0 or top_k <= 0:
                 return None, tables
+            if len(prep) > 3 and prep[3]:
+                return self._run_collapsed(q, top_k, filters, n_live), tables
             # top_k beyond the live rows returns them all (Chroma/FAISS); beyond HR_MAX_K the native
             # search takes its exhaustive exact path (same results, one corpus pass per query)
             return self._index.search(q, min(top_k, n_live), self.filter_bitmap(filters)), tables
@@ -886,6 +959,8 @@ class HipVectorStore(BaseVectorStore):
         """Launch an unfiltered batch through the asynchronous native entry point from the event loop
         (None: this batch takes the worker-thread path -- a filter, no async-capable index, k beyond
         HR_MAX_K, an empty collection, or the store / handle busy: nothing here ever waits)."""
+        if len(prep) > 3 and prep[3]:  # collapsed: the worker-thread route, as filtered batches
+            return None
         q, top_k, filters = prep
         idx = self._index
         if (filters or idx is None or not self.native_async or top_k <= 0 or top_k > _native.HR_MAX_K
@@ -980,12 +1055,16 @@ class HipVectorStore(BaseVectorStore):
         fn = _hostfast.assemble_results if _hostfast is not None else _assemble_results_py
         return fn(Chunk, result_cls, *g, [int(k) for k in ks], [float(t) for t in ths], self.untracked_results)
 
-    async def search(self, query_embedding: list[float], top_k: int = 5, filters: dict[str, Any] | None = None
-                     ) -> list[tuple[Chunk, float]]:
+    async def search(self, query_embedding: list[float], top_k: int = 5, filters: dict[str, Any] | None = None, *,
+                     collapse: bool = False) -> list[tuple[Chunk, float]]:
         if int(top_k) <= 0:
             return []
         q = np.asarray(query_embedding, dtype=np.float32).reshape(-1)
-        return await self._batcher.submit(q, top_k, filters)
+        if not collapse:
+            return await self._batcher.submit(q, top_k, filters)
+        if int(top_k) > _native.HR_MAX_K:  # checked before queueing: a bad query fails alone
+            raise ValueError(f"a collapsed search returns at most {_native.HR_MAX_K} groups (top_k = {top_k})")
+        return await self._batcher.submit(q, top_k, filters, collapse=True)
 
     def get_by_id_sync(self, chunk_id: str) -> Chunk | None:
         with self._lock:
