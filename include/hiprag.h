@@ -109,6 +109,25 @@ int hr_index_search(hr_index* h, const float* q, int B, int k, const uint64_t* r
                     int64_t* rows_out);
 int hr_index_search_device(hr_index* h, const float* q_dev, int B, int k, const uint64_t* row_mask_dev,
                            float* scores_out_dev, int64_t* rows_out_dev, void* stream);
+/* Mixed-filter batches: every query carries its own row mask and the batch still shares one exact scan per 64
+ * queries (each agent searches its own files: kb_file_search builds a where-clause per call, kb_search_toolkit.py;
+ * one hr_index_search per distinct filter is one launch, and with dense filters one corpus read, per filter).
+ * masks: D row bitmaps of the same format as row_mask, mask_stride 64-bit words apart (mask_stride * 64 >= the
+ * index's row count, else HR_E_INVALID); mask_of[i]: the bitmap of query i, or -1 = no mask (outside [-1, D):
+ * HR_E_INVALID).  Query i gets exactly what hr_index_search(h, q_i, 1, k, masks + mask_of[i] * mask_stride, ...)
+ * gives: the same rows, order (canonical fp64 score desc, row asc) and fp32 score bits, -inf / -1 past the live,
+ * allowed rows.  D = 0 or every entry -1 is the unmasked search.  Any k (k > HR_MAX_K: the exhaustive pass per
+ * query with that query's bitmap).  Per chunk of 64 queries (32 above 1280 dims) the scans visit the tiles SOME
+ * query allows (the union of the referenced bitmaps; a dense union or a query without a mask keeps the full scan)
+ * and apply a per-query predicate in the SAMPLE and the FILTER; queries whose exactness guard fails go through the
+ * single-mask collect fallback, once per distinct bitmap among them.  A multi-device handle: HR_E_UNSUPPORTED (run
+ * one hr_index_search per distinct mask).  The device form takes every pointer in device memory (mask_of
+ * included), is ordered after the work queued on `stream` and returns with it idle. */
+int hr_index_search_masks(hr_index* h, const float* q, int B, int k, const uint64_t* masks, int D, int64_t mask_stride,
+                          const int32_t* mask_of, float* scores_out, int64_t* rows_out);
+int hr_index_search_masks_device(hr_index* h, const float* q_dev, int B, int k, const uint64_t* masks_dev, int D,
+                                 int64_t mask_stride, const int32_t* mask_of_dev, float* scores_out_dev,
+                                 int64_t* rows_out_dev, void* stream);
 /* Pipelined form of hr_index_search_device (no mask, k <= HR_MAX_K): enqueue a batch and return a
  * ticket; hr_index_search_finalize(ticket) waits for that batch's exactness-guard flags, runs the exact
  * fallback for queries that need it and returns once scores_out/rows_out hold the final results.  A

@@ -58,6 +58,14 @@ int hr_index_graph_replays(hr_index* h, int64_t* out);
 int hr_index_wide_launches(hr_index* h, int64_t* out);
 /* Diagnostics: 256-query FILTER launches issued so far (graph replays not counted). */
 int hr_index_q256_launches(hr_index* h, int64_t* out);
+/* Diagnostics: FILTER launches that ran with per-query row masks (hr_index_search_masks: one per chunk of up to 64
+ * queries that took the main pass; the single-mask fallbacks of queries whose guard failed are not counted). */
+int hr_index_qmask_launches(hr_index* h, int64_t* out);
+/* set_qmask_timing(h, 1) records HIP events around the mask prep of every chunk of hr_index_search_masks (and waits
+ * for them: measurement only); qmask_last_ms then reports, summed over the most recent call's chunks, out[0] = the
+ * union of the bitmaps + the tile-list build (its count read back included), out[1] = the allow-table build (ms). */
+int hr_index_set_qmask_timing(hr_index* h, int on);
+int hr_index_qmask_last_ms(hr_index* h, double out[2]);
 
 /* Diagnostics of the collapsed search (hr_index_search_collapsed): cumulative queries answered from the probe
  * (out[0]) and by the all-rows pass (out[1]).  set_collapse_timing(h, 1) records HIP events around the stages of

@@ -627,10 +627,10 @@ static void set_dyn_tail(ScanArgs& args, int64_t W, uint32_t* dyn_q) {
     }
 }
 
-template <int MT, int DT, int QB, int P, int MODE, bool NT, int TPB = kScanThreads>
+template <int MT, int DT, int QB, int P, int MODE, bool NT, int TPB = kScanThreads, bool QM = false>
 static int launch_scan_t(hr_index* h, Scratch& sc, int cus, const ScanArgs& a, hipStream_t st, int lds) {
     const int ng = std::max(1, a.ng);
-    auto kern = scan_kernel<MT, DT, QB, P, MODE, NT, TPB>();
+    auto kern = scan_kernel<MT, DT, QB, P, MODE, NT, TPB, QM>();
     static std::mutex attr_mu;
     static int attr_lds[64] = {};     // per device: largest dynamic LDS already allowed
     static int occ[64][4] = {};       // per device: blocks/CU for lds buckets (0 = unknown), per instantiation
@@ -680,7 +680,8 @@ static int launch_scan_t(hr_index* h, Scratch& sc, int cus, const ScanArgs& a, h
 }
 
 template <int MT, int DT, int MODE>
-static int launch_scan_p(hr_index* h, Scratch& sc, int cus, const Plan& pl, const ScanArgs& a, hipStream_t st) {
+static int launch_scan_p(hr_index* h, Scratch& sc, int cus, const Plan& pl, const ScanArgs& a, hipStream_t st,
+                         bool qm = false) {
     int lds = scan_lds_bytes(h, pl.QB);
     // SAMPLE reduces its waves' group maxima in LDS: 8 waves x QB*16*64 floats + 8 part ids
     if (MODE == SCAN_SAMPLE) lds = std::max(lds, (kScanThreads / 64) * pl.QB * 16 * 64 * 4 + 64);
@@ -741,6 +742,26 @@ static int launch_scan_p(hr_index* h, Scratch& sc, int cus, const Plan& pl, cons
             return HR_OK;
         }
     }
+    // per-query masks (a.mask is the allow table): the QM instantiations -- one query group, so the SAMPLE reads with
+    // the default policy and the FILTER non-temporally, as above
+    if constexpr (MODE != SCAN_COLLECT) {
+        if (qm) {
+            if (pl.NG != 1 || !a.mask) return set_err(HR_E_INVALID, "per-query masks take one query group per pass");
+            if (MODE == SCAN_FILTER) h->n_qmask++;
+            constexpr bool QNT = MODE == SCAN_FILTER;
+#define HR_SCAN_QM_CASE(QBv, Pv) \
+    if (pl.QB == QBv && pl.P == Pv)  \
+        return launch_scan_t<MT, DT, QBv, Pv, MODE, QNT, kScanThreads, true>(h, sc, cus, a, st, lds);
+            if constexpr (DT == F32) {
+                HR_SCAN_QM_CASE(1, 8) HR_SCAN_QM_CASE(1, 4) HR_SCAN_QM_CASE(2, 4)
+            } else {
+                HR_SCAN_QM_CASE(1, 16) HR_SCAN_QM_CASE(2, 16) HR_SCAN_QM_CASE(1, 8) HR_SCAN_QM_CASE(2, 8)
+                HR_SCAN_QM_CASE(1, 4) HR_SCAN_QM_CASE(2, 4)
+            }
+#undef HR_SCAN_QM_CASE
+            return set_err(HR_E_INVALID, "no per-query-mask scan variant for this plan");
+        }
+    }
 #define HR_SCAN_CASE(QBv, Pv)                                                                     \
     if (pl.QB == QBv && pl.P == Pv)                                                               \
         return dflt ? launch_scan_t<MT, DT, QBv, Pv, MODE, false>(h, sc, cus, a, st, lds)         \
@@ -756,13 +777,13 @@ static int launch_scan_p(hr_index* h, Scratch& sc, int cus, const Plan& pl, cons
 }
 
 static int launch_scan(hr_index* h, Scratch& sc, int cus, const Plan& pl, const ScanArgs& a, int mode,
-                       hipStream_t st) {
+                       hipStream_t st, bool qm = false) {
     return dispatch_dt(scan_dtype(h), [&](auto dt) -> int {
         constexpr int DT = decltype(dt)::value;
         auto go = [&](auto mt) -> int {
             constexpr int MT = decltype(mt)::value;
-            if (mode == SCAN_SAMPLE) return launch_scan_p<MT, DT, SCAN_SAMPLE>(h, sc, cus, pl, a, st);
-            if (mode == SCAN_FILTER) return launch_scan_p<MT, DT, SCAN_FILTER>(h, sc, cus, pl, a, st);
+            if (mode == SCAN_SAMPLE) return launch_scan_p<MT, DT, SCAN_SAMPLE>(h, sc, cus, pl, a, st, qm);
+            if (mode == SCAN_FILTER) return launch_scan_p<MT, DT, SCAN_FILTER>(h, sc, cus, pl, a, st, qm);
             return launch_scan_p<MT, DT, SCAN_COLLECT>(h, sc, cus, pl, a, st);
         };
         if constexpr (DT == F32) {  // fp32 rows: the MFMA type follows the metric (mfma_type)
@@ -1133,18 +1154,35 @@ static __global__ __launch_bounds__(256) void k_trim(const Cand* __restrict__ in
     }
 }
 
+// Per-query row masks of one chunk (hr_index_search_masks): D bitmaps `stride` words apart, the chunk's mask_of
+// entries on the device, the distinct bitmaps they reference, and whether some query has no mask at all
+struct QChunk {
+    const uint64_t* masks;
+    int64_t stride;
+    const int32_t* mask_of_dev;
+    QMaskRefs refs;
+    int nref;
+    bool any_open;
+};
+
 // One chunk of <= Bp queries on this shard.  mode 0: top-kc via SAMPLE+FILTER(groups);
 // mode 1: collect every row with approx >= floor (exact fallback).
 // st_tail: stream of select + rescore (the outputs are ready in its order).  st_tail != st:
 // pipelined (mode 0 only) -- ping-pong scratch set, the scan leaves tail_cus() CUs free and the
 // tail waits for this batch's FILTER by event; st_tail == st: one stream, the synchronous set.
+// qm (mode 0, one stream, one query group, mask_dev null): per-query masks -- the tile list comes from the union of
+// the chunk's bitmaps, the scans are the QM instantiations reading the allow table built here; the shadow-8 scan, the
+// persistent and the wide FILTERs never take such a chunk.
 static int shard_chunk(hr_index* h, const float* q_dev, int B, int kc, int kj, const uint64_t* mask_dev, int64_t row_offset,
                        const double* kth_dev_host /* mode 1: host array of kth, B */, int mode, int cap_out,
                        Cand* cand_out, double* bound_out, hipStream_t st, hipStream_t st_tail,
-                       hipEvent_t q_ready = nullptr, int k8 = 0 /* the search's k: > 0 allows a shadow-8 scan */) {
+                       hipEvent_t q_ready = nullptr, int k8 = 0 /* the search's k: > 0 allows a shadow-8 scan */,
+                       const QChunk* qm = nullptr) {
     if (int rc = shadow_update(h)) return rc;
     Plan pl;
     if (int rc = make_plan(h, B, &pl)) return rc;
+    if (qm && (mode != 0 || st_tail != st || pl.NG != 1 || mask_dev || B > pl.QB * 32))
+        return set_err(HR_E_INVALID, "per-query masks: a synchronous main pass of one query group");
     const int Bp = pl.Bp;
     const bool piped = st_tail != st && mode == 0;
     if (!piped) st_tail = st;
@@ -1192,7 +1230,7 @@ static int shard_chunk(hr_index* h, const float* q_dev, int B, int kc, int kj, c
     // persistent ranges -- the single-stream FILTER's, where it was measured.  It selects and rescores kc8 >= kc
     // candidates and trims them to the caller's kc (kc8_for).
     int kj8 = 0;
-    const int kc8 = (mode == 0 && k8 > 0 && h->rows8 && h->shadow8_lo == INT64_MAX && h->shadow8_mode > 0 &&
+    const int kc8 = (mode == 0 && !qm && k8 > 0 && h->rows8 && h->shadow8_lo == INT64_MAX && h->shadow8_mode > 0 &&
                      h->stripe_G == 1 && pl.NG == 1 && !wide_likely && (h->shadow8_mode == 2 || shadow8_in_range(h)))
                         ? kc8_for(k8, kc, h->dim, &kj8)
                         : 0;
@@ -1203,7 +1241,7 @@ static int shard_chunk(hr_index* h, const float* q_dev, int B, int kc, int kj, c
         kj = kj8;
         h->last_kc8 = kc8;
     }
-    const bool persist = mode == 0 && !wide_likely && !use8 &&
+    const bool persist = mode == 0 && !wide_likely && !use8 && !qm &&
                          persist_wanted(h, pl, (kc + 31) / 32, early, mask_dev, n_tiles);
     uint32_t pepoch = 0;
     int pslot = 0;
@@ -1240,6 +1278,20 @@ static int shard_chunk(hr_index* h, const float* q_dev, int B, int kc, int kj, c
     // row -- from the host-mask path (hr_index_search built h->tl), or built here for a device mask
     // (rocPRIM select on the prep stream; the count is read back, so a masked batch costs one host
     // wait for the prep stream).  A dense mask (more than half the tiles) keeps the full scan.
+    const bool qm_timed = qm && h->qmask_timing;
+    if (qm_timed) {
+        for (auto& e : h->qm_ev)
+            if (!e) HIP_TRY(hipEventCreate(&e));
+        HIP_TRY(hipEventRecord(h->qm_ev[0], sp));
+    }
+    if (qm && !qm->any_open && n_tiles > 0) {
+        // the union of the chunk's bitmaps stands in for the row mask of the tile-list builder below; with a query
+        // that has no mask the union is all ones: no list
+        HIP_TRY(sc.qunion.ensure((size_t)n_tiles * 4));
+        if (int rc = launch_qmask_union(qm->masks, qm->stride, qm->refs, qm->nref, n_tiles, sc.qunion.as<uint32_t>(), sp))
+            return set_err(rc, "mask union launch failed");
+        mask_dev = sc.qunion.as<uint64_t>();
+    }
     const uint32_t* tl_ptr = nullptr;
     int64_t n_vis = n_tiles;
     if (h->tl_n >= 0) {
@@ -1259,6 +1311,23 @@ static int shard_chunk(hr_index* h, const float* q_dev, int B, int kc, int kj, c
         if ((int64_t)cnt_h * 2 <= n_tiles) {
             tl_ptr = list;
             n_vis = cnt_h;
+        }
+    }
+    if (qm) {
+        if (qm_timed) HIP_TRY(hipEventRecord(h->qm_ev[1], sp));
+        mask_dev = nullptr;  // (the union only chose the tiles: the predicate is the allow table's)
+        HIP_TRY(sc.qallow.ensure(std::max<size_t>(256, (size_t)n_tiles * 64 * 4)));
+        if (int rc = launch_qallow_build(qm->masks, qm->stride, qm->mask_of_dev, B, pl.QB, h->live, tl_ptr, n_vis,
+                                         sc.qallow.as<uint32_t>(), sp))
+            return set_err(rc, "allow table launch failed");
+        if (qm_timed) {
+            HIP_TRY(hipEventRecord(h->qm_ev[2], sp));
+            HIP_TRY(hipEventSynchronize(h->qm_ev[2]));
+            float a_ms = 0.f, b_ms = 0.f;
+            HIP_TRY(hipEventElapsedTime(&a_ms, h->qm_ev[0], h->qm_ev[1]));
+            HIP_TRY(hipEventElapsedTime(&b_ms, h->qm_ev[1], h->qm_ev[2]));
+            h->qm_ms[0] += a_ms;
+            h->qm_ms[1] += b_ms;
         }
     }
     const int64_t s_target = sample_target(n_vis);
@@ -1341,7 +1410,7 @@ static int shard_chunk(hr_index* h, const float* q_dev, int B, int kc, int kj, c
     a.rscale = use8 ? h->scale8 : nullptr;
     a.xnorm = h->metric == L2 ? h->xnorm : nullptr;
     a.live = h->live;
-    a.mask = (const uint32_t*)mask_dev;
+    a.mask = qm ? sc.qallow.as<uint32_t>() : (const uint32_t*)mask_dev;  // (QM scans: the allow table)
     a.qfrag = sc.qfrag.as<uint16_t>();
     a.S = h->S;
     a.mkeys = sc.mkeys.as<uint32_t>();
@@ -1399,7 +1468,7 @@ static int shard_chunk(hr_index* h, const float* q_dev, int B, int kc, int kj, c
             a.n_units = (n_vis + a.sample_stride - 1) / a.sample_stride;
             if (timed) HIP_TRY(hipEventRecord(ev.e[0], sp));
             if (int rc = use8 ? launch_scan8<SCAN_SAMPLE>(h, sc, early ? spare : cus, pl, a, sp)
-                              : launch_scan(h, sc, early ? spare : cus, pl, a, SCAN_SAMPLE, sp))
+                              : launch_scan(h, sc, early ? spare : cus, pl, a, SCAN_SAMPLE, sp, qm != nullptr))
                 return rc;
             // a strided sample: start the thresholds at the kj-th largest sampled group maximum (k_floor_kth; a
             // sample of every tile -- small shards -- leaves the floor)
@@ -1470,7 +1539,7 @@ static int shard_chunk(hr_index* h, const float* q_dev, int B, int kc, int kj, c
         } else {
             if (timed) HIP_TRY(hipEventRecord(ev.e[1], sf));
             if (int rc = use8 ? launch_scan8<SCAN_FILTER>(h, sc, cus, pl, a, sf)
-                              : launch_scan(h, sc, cus, pl, a, groups ? SCAN_FILTER : SCAN_COLLECT, sf))
+                              : launch_scan(h, sc, cus, pl, a, groups ? SCAN_FILTER : SCAN_COLLECT, sf, qm != nullptr))
                 return rc;
         }
         if (timed) {
@@ -1672,6 +1741,174 @@ static int search_device_impl(hr_index* h, const float* q_dev, int B, int k, con
         if (fail[(size_t)b]) failed.push_back(b);
     if (failed.empty()) return HR_OK;
     return search_fallback(h, q_dev, k, mask_dev, s_out, r_out, failed, kth.data(), st);
+}
+
+// hr_index_search_masks on device-resident queries, bitmaps and mask_of (mask_of_host: the same entries, already
+// validated): consecutive chunks of one query group through the QM main pass, one merge, then the queries whose
+// guard failed through the single-mask fallback, once per distinct bitmap among them
+static int search_masks_impl(hr_index* h, const float* q_dev, int B, int k, const uint64_t* masks_dev, int64_t stride,
+                             const int32_t* mask_of_dev, const int32_t* mask_of_host, float* s_out, int64_t* r_out,
+                             hipStream_t st) {
+    if (int rc = validate_search(h, B, k)) return rc;
+    bool any_mask = false;
+    for (int b = 0; b < B; ++b) any_mask = any_mask || mask_of_host[b] >= 0;
+    h->qm_ms[0] = h->qm_ms[1] = 0.0;
+    if (!any_mask) return search_device_impl(h, q_dev, B, k, nullptr, s_out, r_out, st);
+    const int kc = hr_kc_for_k_dim(k, h->dim);
+    HIP_TRY(h->cand.ensure((size_t)B * kc * sizeof(Cand)));
+    HIP_TRY(h->bound.ensure((size_t)B * 8));
+    HIP_TRY(h->kth.ensure((size_t)B * 8));
+    HIP_TRY(h->fail.ensure((size_t)B * 4));
+    Plan pl0;
+    if (int rc = make_plan(h, std::min(B, 64), &pl0)) return rc;
+    const int chunk = pl0.QB * 32;  // one query group: 64 queries, 32 where LDS holds one query block (dims > 1280)
+    for (int b0 = 0; b0 < B; b0 += chunk) {
+        const int bc = std::min(chunk, B - b0);
+        QChunk qc{};
+        qc.masks = masks_dev;
+        qc.stride = stride;
+        qc.mask_of_dev = mask_of_dev + b0;
+        for (int b = b0; b < b0 + bc; ++b) {
+            const int d = mask_of_host[b];
+            if (d < 0) {
+                qc.any_open = true;
+                continue;
+            }
+            bool seen = false;
+            for (int r = 0; r < qc.nref; ++r) seen = seen || qc.refs.d[r] == d;
+            if (!seen) qc.refs.d[qc.nref++] = d;
+        }
+        if (int rc = shard_chunk(h, q_dev + (int64_t)b0 * h->dim, bc, kc, hr_rank_for(k, kc, h->dim), nullptr, 0, nullptr, 0,
+                                 0, h->cand.as<Cand>() + (int64_t)b0 * kc, h->bound.as<double>() + b0, st, st, nullptr, 0,
+                                 &qc))
+            return rc;
+    }
+    if (int rc = launch_merge(h->device, h->cand.as<Cand>(), h->bound.as<double>(), 1, B, kc, k, s_out, r_out,
+                              h->kth.as<double>(), h->fail.as<int32_t>(), st))
+        return rc;
+    std::vector<int32_t> fail((size_t)B);
+    std::vector<double> kth((size_t)B);
+    HIP_TRY(hipMemcpyAsync(fail.data(), h->fail.p, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(kth.data(), h->kth.p, (size_t)B * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    std::vector<char> done((size_t)B, 0);
+    for (int b = 0; b < B; ++b) {
+        if (!fail[(size_t)b] || done[(size_t)b]) continue;
+        const int d = mask_of_host[b];
+        std::vector<int> failed;
+        for (int c = b; c < B; ++c)
+            if (fail[(size_t)c] && mask_of_host[c] == d) {
+                failed.push_back(c);
+                done[(size_t)c] = 1;
+            }
+        if (int rc = search_fallback(h, q_dev, k, d < 0 ? nullptr : masks_dev + (int64_t)d * stride, s_out, r_out, failed,
+                                     kth.data(), st))
+            return rc;
+    }
+    return HR_OK;
+}
+
+static int validate_masks(hr_index* h, int B, int D, int64_t stride, const int32_t* mask_of_host) {
+    if (B <= 0) return set_err(HR_E_INVALID, "B must be positive");
+    if (D < 0) return set_err(HR_E_INVALID, "D must not be negative");
+    if (D > 0 && stride * 64 < h->n) return set_err(HR_E_INVALID, "row masks shorter than the index");
+    for (int b = 0; b < B; ++b)
+        if (mask_of_host[b] < -1 || mask_of_host[b] >= D) return set_err(HR_E_INVALID, "mask_of entry outside [-1, D)");
+    return HR_OK;
+}
+
+// k > HR_MAX_K with per-query masks: the exhaustive pass per query with that query's bitmap, into host arrays
+static int masks_exact_all(hr_index* h, const float* q_dev, int B, int k, const uint64_t* masks_dev, int64_t stride,
+                           const int32_t* mask_of_host, float* scores_out, int64_t* rows_out, hipStream_t st) {
+    std::vector<Cand> c((size_t)k);
+    for (int b = 0; b < B; ++b) {
+        const int d = mask_of_host[b];
+        if (int rc = index_exact_all(h, q_dev + (int64_t)b * h->dim, 1, k, d < 0 ? nullptr : masks_dev + (int64_t)d * stride,
+                                     c.data(), st))
+            return rc;
+        for (int i = 0; i < k; ++i) {
+            scores_out[(size_t)b * k + i] = c[(size_t)i].row >= 0 ? (float)c[(size_t)i].score : -INFINITY;
+            rows_out[(size_t)b * k + i] = c[(size_t)i].row;
+        }
+    }
+    return HR_OK;
+}
+
+extern "C" int hr_index_search_masks_device(hr_index* h, const float* q_dev, int B, int k, const uint64_t* masks_dev, int D,
+                                            int64_t mask_stride, const int32_t* mask_of_dev, float* scores_out_dev,
+                                            int64_t* rows_out_dev, void* stream) {
+    if (!h || !q_dev || !scores_out_dev || !rows_out_dev || !mask_of_dev || (D > 0 && !masks_dev))
+        return set_err(HR_E_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (h->G > 1) return set_err(HR_E_UNSUPPORTED, "per-query masks need a single-device handle");
+    if (int rc = set_device(h)) return rc;
+    if (int rc = persist_close(h)) return rc;  // a running persistent FILTER leaves the CUs to this search
+    if (B <= 0) return set_err(HR_E_INVALID, "B must be positive");
+    if (k <= 0) return set_err(HR_E_INVALID, "k must be positive");
+    hipStream_t st = (hipStream_t)stream;
+    std::vector<int32_t> of((size_t)B);
+    HIP_TRY(hipMemcpyAsync(of.data(), mask_of_dev, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (int rc = validate_masks(h, B, D, mask_stride, of.data())) return rc;
+    if (k > HR_MAX_K) {
+        std::vector<float> s((size_t)B * k);
+        std::vector<int64_t> r((size_t)B * k);
+        if (int rc = masks_exact_all(h, q_dev, B, k, masks_dev, mask_stride, of.data(), s.data(), r.data(), st)) return rc;
+        HIP_TRY(hipMemcpyAsync(scores_out_dev, s.data(), s.size() * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(rows_out_dev, r.data(), r.size() * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return HR_OK;
+    }
+    if (int rc = search_masks_impl(h, q_dev, B, k, masks_dev, mask_stride, mask_of_dev, of.data(), scores_out_dev,
+                                   rows_out_dev, st))
+        return rc;
+    HIP_TRY(hipStreamSynchronize(st));
+    return HR_OK;
+}
+
+extern "C" int hr_index_search_masks(hr_index* h, const float* q, int B, int k, const uint64_t* masks, int D,
+                                     int64_t mask_stride, const int32_t* mask_of, float* scores_out, int64_t* rows_out) {
+    if (!h || !q || !scores_out || !rows_out || !mask_of || (D > 0 && !masks)) return set_err(HR_E_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (h->G > 1) return set_err(HR_E_UNSUPPORTED, "per-query masks need a single-device handle");
+    if (int rc = set_device(h)) return rc;
+    if (int rc = persist_close(h)) return rc;
+    if (k <= 0) return set_err(HR_E_INVALID, "k must be positive");
+    if (int rc = validate_masks(h, B, D, mask_stride, mask_of)) return rc;
+    if (h->n_live == 0) {
+        for (int64_t i = 0; i < (int64_t)B * k; ++i) {
+            scores_out[i] = -INFINITY;
+            rows_out[i] = -1;
+        }
+        return HR_OK;
+    }
+    hipStream_t st = h->stream;
+    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t kk = (size_t)std::min(k, HR_MAX_K);  // (k > HR_MAX_K writes the host arrays directly)
+    const size_t off_r = up((size_t)B * kk * 4);
+    HIP_TRY(h->q_in.ensure((size_t)B * h->dim * 4));
+    HIP_TRY(h->stage.ensure(off_r + up((size_t)B * kk * 8)));
+    HIP_TRY(h->qm_of.ensure((size_t)B * 4));
+    // only the words that cover the index go up: D bitmaps, words64 apart on the device
+    const int64_t words64 = (h->n + 63) / 64;
+    HIP_TRY(h->qm_masks.ensure(std::max<size_t>(8, (size_t)D * words64 * 8)));
+    float* s_dev = h->stage.as<float>();
+    int64_t* r_dev = (int64_t*)(h->stage.as<uint8_t>() + off_r);
+    HIP_TRY(hipMemcpyAsync(h->q_in.p, q, (size_t)B * h->dim * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(h->qm_of.p, mask_of, (size_t)B * 4, hipMemcpyHostToDevice, st));
+    if (D > 0)
+        HIP_TRY(hipMemcpy2DAsync(h->qm_masks.p, (size_t)words64 * 8, masks, (size_t)mask_stride * 8, (size_t)words64 * 8,
+                                 (size_t)D, hipMemcpyHostToDevice, st));
+    if (k > HR_MAX_K)
+        return masks_exact_all(h, h->q_in.as<float>(), B, k, h->qm_masks.as<uint64_t>(), words64, mask_of, scores_out,
+                               rows_out, st);
+    if (int rc = search_masks_impl(h, h->q_in.as<float>(), B, k, h->qm_masks.as<uint64_t>(), words64, h->qm_of.as<int32_t>(),
+                                   mask_of, s_dev, r_dev, st))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(scores_out, s_dev, (size_t)B * k * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(rows_out, r_dev, (size_t)B * k * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return HR_OK;
 }
 
 // hr_index_search through a captured HIP graph (no mask, k <= HR_MAX_K, untimed): the host work of a
@@ -2552,10 +2789,12 @@ extern "C" void hr_index_destroy(hr_index* h) {
         if (g.exec) (void)hipGraphExecDestroy(g.exec);
     if (h->pin) (void)hipHostFree(h->pin);
     for (DevBuf* b : {&h->q_in, &h->cand, &h->bound, &h->kth, &h->fail, &h->fb_cand, &h->fb_bound, &h->fb_q,
-                      &h->fb_out, &h->stage, &h->exh, &h->tl, &h->s_mask, &h->sync_out,
+                      &h->fb_out, &h->stage, &h->exh, &h->tl, &h->s_mask, &h->sync_out, &h->qm_masks, &h->qm_of,
                       &h->ivf_coarse, &h->ivf_probe, &h->ivf_units, &h->ivf_uoff, &h->ivf_out})
         b->release();
     for (auto& sc : h->scr) sc.release_all();
+    for (auto& e : h->qm_ev)
+        if (e) (void)hipEventDestroy(e);
     for (auto* list : {&h->ev_free})
         for (auto& ev : *list)
             for (auto& x : ev.e) (void)hipEventDestroy(x);
@@ -2840,6 +3079,28 @@ extern "C" int hr_index_set_q256(hr_index* h, int on) {
     }
     h->q256 = on != 0;
     for (hr_index* s : h->shards) s->q256 = on != 0;
+    return HR_OK;
+}
+
+extern "C" int hr_index_qmask_launches(hr_index* h, int64_t* out) {
+    if (!h || !out) return set_err(HR_E_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    *out = h->n_qmask;
+    return HR_OK;
+}
+
+extern "C" int hr_index_set_qmask_timing(hr_index* h, int on) {
+    if (!h) return set_err(HR_E_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    h->qmask_timing = on != 0;
+    return HR_OK;
+}
+
+extern "C" int hr_index_qmask_last_ms(hr_index* h, double out[2]) {
+    if (!h || !out) return set_err(HR_E_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    out[0] = h->qm_ms[0];
+    out[1] = h->qm_ms[1];
     return HR_OK;
 }
 

@@ -80,6 +80,17 @@ int launch_merge_sorted(const Cand* cand, int64_t cstride, int G, int B, int m, 
 size_t tile_list_scratch_bytes(int64_t n_tiles);
 int build_tile_list(const uint32_t* live, const uint32_t* mask, int64_t n_tiles, uint32_t* list, uint32_t* count,
                     void* scratch, size_t scratch_bytes, hipStream_t st);
+// hr_qmask.hip: per-query row masks (hr_index_search_masks).  QMaskRefs: the distinct bitmaps a chunk of <= 64
+// queries references; launch_qmask_union ORs them into one u32 word per tile; launch_qallow_build writes the
+// lane-order allow words ([tile][64], what the QM scans read through ScanArgs::mask) of the n_units visited tiles for the chunk's B <= QB * 32
+// queries (mask_of: B device entries in [-1, D), -1 = no mask)
+struct QMaskRefs {
+    int32_t d[64];
+};
+int launch_qmask_union(const uint64_t* masks, int64_t stride, const QMaskRefs& refs, int nref, int64_t n_tiles,
+                       uint32_t* out, hipStream_t st);
+int launch_qallow_build(const uint64_t* masks, int64_t stride, const int32_t* mask_of, int B, int QB, const uint32_t* live,
+                        const uint32_t* tile_list, int64_t n_units, uint32_t* qallow, hipStream_t st);
 // hr_wide.hip: the 128-query FILTER (one workgroup per CU, 4 waves; pbuf / pcnt regions [2 groups][4 * cus][64])
 struct ScanArgs;
 bool wide_filter_ok(int dtype, int S);
@@ -112,7 +123,9 @@ struct Scratch {
     DevBuf q32, qfrag, qerr, mkeys, floor_q, cnt, buf, sel_rows, sel_cnt, bound_approx, overflow, pbuf, pcnt, dyn_q,
         tl, tl_tmp,  // device-mask tile list (+ its count after the list) and its rocPRIM scratch
         wtiles,      // diagnostics: tiles each wave of the most recent FILTER launch scanned (ScanArgs::wave_tiles)
-        cand8;       // shadow-8 scan: the exact candidates of its deeper kc, before the trim to the caller's kc
+        cand8,       // shadow-8 scan: the exact candidates of its deeper kc, before the trim to the caller's kc
+        qunion,      // per-query masks: OR of the chunk's bitmaps, one word per tile (the tile list's mask)
+        qallow;      // per-query masks: lane-order allow words, [tile][64] (the QM scans' ScanArgs::mask)
     int64_t last_W = 0, last_Bp = 0;  // waves (per query group) and queries per group of the most recent FILTER
     int last_ng = 1;                  // query groups of that launch
     int last_capw = kCapW;            // candidate slots per (region, query) of that launch
@@ -124,7 +137,7 @@ struct Scratch {
     bool armed = false;               // `released` has been recorded at least once
     void release_all() {
         for (DevBuf* b : {&q32, &qfrag, &qerr, &mkeys, &floor_q, &cnt, &buf, &sel_rows, &sel_cnt, &bound_approx,
-                          &overflow, &pbuf, &pcnt, &dyn_q, &tl, &tl_tmp, &wtiles, &cand8})
+                          &overflow, &pbuf, &pcnt, &dyn_q, &tl, &tl_tmp, &wtiles, &cand8, &qunion, &qallow})
             b->release();
         if (scanned) (void)hipEventDestroy(scanned);
         if (released) (void)hipEventDestroy(released);
@@ -203,6 +216,11 @@ struct hr_index {
     int64_t n_guard_fail = 0;         // queries that failed the exactness guard (collect fallback)
     int64_t n_wide = 0;               // 128-query FILTER launches issued (hr_wide.hip; not graph replays)
     int64_t n_q256 = 0;               // 256-query FILTER launches issued (hr_q256.hip)
+    int64_t n_qmask = 0;              // FILTER launches that ran with per-query masks (hr_index_search_masks)
+    DevBuf qm_masks, qm_of;           // hr_index_search_masks (host form): the D bitmaps and mask_of on the device
+    bool qmask_timing = false;        // hr_index_set_qmask_timing: HIP events around the mask prep of every chunk
+    hipEvent_t qm_ev[3] = {nullptr, nullptr, nullptr};
+    double qm_ms[2] = {0.0, 0.0};     // union + tile list, allow table: summed over the most recent call's chunks
     bool q256 = true;                 // hr_index_set_q256: 129-256-query batches take the 256-query FILTER
     std::vector<float> floor_host;
     // ---- hr_index_search (host queries, no mask) replayed as one HIP graph per batch shape: H2D of

@@ -237,6 +237,10 @@ struct ScanArgs {
     const uint8_t* rows;     // tiled corpus
     const uint32_t* live;    // one word per tile
     const uint32_t* mask;    // one word per tile (u64 row bitmap viewed as u32), nullable
+    // QM instantiations (per-query row masks, hr_qmask.hip) read `mask` as the allow table instead, never null: one
+    // word per lane per tile, [tile][64] -- bit qb*16+i of lane l's word = row slot_row(tile, l & 31) is live and
+    // allowed for the query that accumulator register (qb, i) of that lane holds (acc_query(qb, i, l >> 5)); the
+    // bits of padded queries are 0.  (No field of its own: the kernel arguments of the other instantiations stay as they are.)
     const uint16_t* qfrag;   // [S][QB][64][8]
     int S;
     int64_t n_units;         // tiles (FILTER) or sample tiles (SAMPLE)
@@ -506,11 +510,14 @@ enum { SCAN_SAMPLE = 0, SCAN_FILTER = 1, SCAN_COLLECT = 2 };
 // LEAN (the persistent FILTER, hr_persist.hip): one query group, one row part, no mask or tile list, round-robin
 // units -- fixed at compile time, which frees the scalar registers those cases take (the persistent loop around the
 // body needs a few of its own, and this body is at the 256-VGPR limit with SGPRs spilled to VGPR lanes).
-template <int MT, int DT, int QB, int P, int MODE, bool NT, int TPB, bool LEAN = false>
+// QM (SAMPLE / FILTER of a batch with per-query row masks): the live / mask word shared by the 64 queries gives way
+// to the lane's allow word (ScanArgs::mask, read as the allow table), one bit per accumulator register.
+template <int MT, int DT, int QB, int P, int MODE, bool NT, int TPB, bool LEAN = false, bool QM = false>
 __device__ __forceinline__ void scan_body(ScanArgs a) {
     constexpr bool FILTER = MODE != SCAN_SAMPLE;
     constexpr bool priv = MODE == SCAN_FILTER;
     static_assert(!LEAN || MODE == SCAN_FILTER, "the lean body is a FILTER");
+    static_assert(!QM || (!LEAN && MODE != SCAN_COLLECT && DT != I8S), "per-query masks: the plain SAMPLE / FILTER");
     if constexpr (LEAN) {
         a.ng = 1;
         a.np = 1;
@@ -793,7 +800,8 @@ __device__ __forceinline__ void scan_body(ScanArgs a) {
     uint32_t rkey[QB][16];  // group-max keys of the refresh due in the current tile's epilogue
     // (LEAN: never -- the 32 keys held across the k-loop cost the registers the persistent loop needs)
     // (nor for the 8-bit shadow, whose two converted fragments per ring entry take the registers)
-    const bool early_refresh = !LEAN && DT != I8S && a.early_refresh != 0;
+    // (nor with per-query masks: the allow word held across the k-loop and its 16*QB bit tests take them too)
+    const bool early_refresh = !LEAN && DT != I8S && !QM && a.early_refresh != 0;
     int64_t u = u0, u_end = u1, pend = -1, done = 0;
     // a.stagger: refreshes staggered over the workgroup's waves (wave v refreshes after tiles with (done + v) % RT
     // == 0) -- each tile some waves publish and read fresh keys instead of all of them every RT-th tile.  Large
@@ -851,8 +859,15 @@ __device__ __forceinline__ void scan_body(ScanArgs a) {
         // this tile's live / mask words, issued before the k-loop: read in the epilogue, they are then
         // older than the ring loads in flight (a load issued after them would make that read wait for
         // the whole ring: vmcnt(0) at every tile)
-        uint32_t allow = scalar_word(a.live, t);
-        if (a.mask) allow &= scalar_word(a.mask, t);
+        uint32_t allow = QM ? 0u : scalar_word(a.live, t);
+        if (!QM && a.mask) allow &= scalar_word(a.mask, t);
+        // per-query masks: this lane's allow word, issued like the shadow-8 row scale below (older than every ring
+        // load the k-loop issues, so the loop's own ring waits retire it) and used in the epilogue
+        uint32_t aw = 0;
+        if constexpr (QM) {
+            aw = a.mask[t * 64 + lane];
+            asm volatile("" ::: "memory");
+        }
         // 8-bit shadow: this lane's row scale, issued like a refresh's loads before the k-loop (older than every
         // ring load the loop issues, so the loop's own ring waits retire it) and used in the epilogue
         float rsc = 1.0f;
@@ -922,6 +937,8 @@ __device__ __forceinline__ void scan_body(ScanArgs a) {
                 for (int i = 0; i < 16; ++i) acc[qb][i] *= rsc;
         }
         const bool ok = (allow >> rg) & 1u;
+        // the predicate of accumulator register (qb, i): shared by the queries, or (QM) that query's bit of the allow word
+#define HR_OKR(qb, i) (QM ? ((aw >> ((qb) * 16 + (i))) & 1u) != 0 : ok)
         const uint32_t row = (uint32_t)(t * 32 + rg);
         // regs: the accumulator registers (bit qb*16+i, wave-uniform) holding a passing score; the
         // append pass below visits only those (a scalar bit test per register instead of a compare +
@@ -932,9 +949,9 @@ __device__ __forceinline__ void scan_body(ScanArgs a) {
         for (int qb = 0; qb < QB; ++qb)
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
-                const float v = ok ? acc[qb][i] : -__builtin_inff();
+                const float v = HR_OKR(qb, i) ? acc[qb][i] : -__builtin_inff();
                 gmax[qb][i] = fmaxf(gmax[qb][i], v);
-                if (FILTER) regs |= (__ballot(ok && v >= th[qb][i]) != 0 ? 1u : 0u) << (qb * 16 + i);
+                if (FILTER) regs |= (__ballot(HR_OKR(qb, i) && v >= th[qb][i]) != 0 ? 1u : 0u) << (qb * 16 + i);
             }
         if (FILTER && regs && !(HR_DIAG & 1)) {
 #pragma unroll
@@ -943,7 +960,7 @@ __device__ __forceinline__ void scan_body(ScanArgs a) {
                 for (int i = 0; i < 16; ++i) {
                     if (!((regs >> (qb * 16 + i)) & 1u)) continue;
                     const float v = acc[qb][i];
-                    const bool pass = ok && v >= th[qb][i];
+                    const bool pass = HR_OKR(qb, i) && v >= th[qb][i];
                     const uint64_t m = __ballot(pass);
                     if (m) {
 #pragma unroll
@@ -980,6 +997,7 @@ __device__ __forceinline__ void scan_body(ScanArgs a) {
                     }
                 }
         }
+#undef HR_OKR
         ++done;
         if (MODE == SCAN_FILTER && !(HR_DIAG & 2) && ((done + roff) % a.refresh_every) == 0) {
             if (rdue) refresh_apply(rkey, true, false);
@@ -1047,22 +1065,22 @@ __device__ __forceinline__ void scan_body(ScanArgs a) {
 
 
 // (2nd launch bound: min waves per SIMD)
-template <int MT, int DT, int QB, int P, bool NT, int TPB>
+template <int MT, int DT, int QB, int P, bool NT, int TPB, bool QM = false>
 __global__ __launch_bounds__(TPB, TPB >= 512 ? 2 : 1) void k_scan_sample(ScanArgs a) {
-    scan_body<MT, DT, QB, P, SCAN_SAMPLE, NT, TPB>(a);
+    scan_body<MT, DT, QB, P, SCAN_SAMPLE, NT, TPB, false, QM>(a);
 }
-template <int MT, int DT, int QB, int P, bool NT, int TPB>
+template <int MT, int DT, int QB, int P, bool NT, int TPB, bool QM = false>
 __global__ __launch_bounds__(TPB, TPB >= 512 ? 2 : 1) void k_scan_filter(ScanArgs a) {
-    scan_body<MT, DT, QB, P, SCAN_FILTER, NT, TPB>(a);
+    scan_body<MT, DT, QB, P, SCAN_FILTER, NT, TPB, false, QM>(a);
 }
 template <int MT, int DT, int QB, int P, bool NT, int TPB>
 __global__ __launch_bounds__(TPB, TPB >= 512 ? 2 : 1) void k_scan_collect(ScanArgs a) {
     scan_body<MT, DT, QB, P, SCAN_COLLECT, NT, TPB>(a);
 }
-template <int MT, int DT, int QB, int P, int MODE, bool NT, int TPB>
+template <int MT, int DT, int QB, int P, int MODE, bool NT, int TPB, bool QM = false>
 constexpr auto scan_kernel() {
-    if constexpr (MODE == SCAN_SAMPLE) return &k_scan_sample<MT, DT, QB, P, NT, TPB>;
-    else if constexpr (MODE == SCAN_FILTER) return &k_scan_filter<MT, DT, QB, P, NT, TPB>;
+    if constexpr (MODE == SCAN_SAMPLE) return &k_scan_sample<MT, DT, QB, P, NT, TPB, QM>;
+    else if constexpr (MODE == SCAN_FILTER) return &k_scan_filter<MT, DT, QB, P, NT, TPB, QM>;
     else return &k_scan_collect<MT, DT, QB, P, NT, TPB>;
 }
 

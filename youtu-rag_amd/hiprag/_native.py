@@ -58,6 +58,8 @@ EXPORTS = [
     "hr_index_shadow8_stats", "hr_index_create_ex", "hr_index_load_ex", "hr_index_copy_rows", "hr_ivf_search_ext",
     "hr_ivf_position_mask", "hr_index_set_groups", "hr_index_search_collapsed", "hr_index_search_collapsed_device",
     "hr_index_collapse_stats", "hr_index_set_collapse_timing", "hr_index_collapse_last_ms",
+    "hr_index_search_masks", "hr_index_search_masks_device", "hr_index_qmask_launches",
+    "hr_index_set_qmask_timing", "hr_index_qmask_last_ms",
 ]
 
 _lib = None
@@ -206,6 +208,11 @@ def load_library(path: str | None = None):
             "hr_index_collapse_stats": [vp, vp],
             "hr_index_set_collapse_timing": [vp, i32],
             "hr_index_collapse_last_ms": [vp, vp],
+            "hr_index_search_masks": [vp, vp, i32, i32, vp, i32, i64, vp, vp, vp],
+            "hr_index_search_masks_device": [vp, vp, i32, i32, vp, i32, i64, vp, vp, vp, vp],
+            "hr_index_qmask_launches": [vp, vp],
+            "hr_index_set_qmask_timing": [vp, i32],
+            "hr_index_qmask_last_ms": [vp, vp],
         }
         for name, args in sig.items():
             if p != (path or LIB_PATH) and not hasattr(L, name):
@@ -383,6 +390,64 @@ class NativeIndex:
                                  f"(needs {(n_rows + 63) // 64})")
         _check(self.lib.hr_index_search(self._h, _ptr(q), B, int(k), _ptr(m), _ptr(s), _ptr(r)))
         return s, r
+
+    def search_masks(self, q: np.ndarray, k: int, masks, mask_of) -> tuple[np.ndarray, np.ndarray]:
+        """search() with one row mask PER QUERY in one call (hr_index_search_masks): ``masks`` is a (D, words) uint64
+        array of row bitmaps (or a list of D equally long ones), ``mask_of[i]`` the bitmap of query i, -1 = none.
+        Query i gets exactly what ``search(q[i], k, masks[mask_of[i]])`` gives.  A multi-device handle raises
+        NotImplementedError: group the queries by mask and call search()."""
+        q = np.ascontiguousarray(q, np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.shape[1] != self.dim:
+            raise ValueError(f"query dim {q.shape[1]} != index dim {self.dim}")
+        B = q.shape[0]
+        of = np.ascontiguousarray(np.asarray(mask_of, np.int32).reshape(-1))
+        if len(of) != B:
+            raise ValueError(f"mask_of has {len(of)} entries for {B} queries")
+        m = np.ascontiguousarray(masks, np.uint64) if masks is not None and len(masks) else np.zeros((0, 0), np.uint64)
+        if m.ndim == 1:
+            m = m[None, :]
+        D, words = int(m.shape[0]), int(m.shape[1]) if m.ndim == 2 else 0
+        if D:
+            n_rows = self.size()[0]
+            if words * 64 < n_rows:  # the library reads one bit per index row
+                raise ValueError(f"row mask has {words} words, the index {n_rows} rows "
+                                 f"(needs {(n_rows + 63) // 64})")
+        s = np.empty((B, k), np.float32)
+        r = np.empty((B, k), np.int64)
+        _check(self.lib.hr_index_search_masks(self._h, _ptr(q), B, int(k), _ptr(m) if D else None, D, words, _ptr(of),
+                                              _ptr(s), _ptr(r)))
+        return s, r
+
+    def search_masks_device(self, q_ptr: int, B: int, k: int, scores_ptr: int, rows_ptr: int, masks_ptr: int, D: int,
+                            mask_stride: int, mask_of_ptr: int, stream: int = 0) -> None:
+        """search_masks() with every array in device memory (D bitmaps ``mask_stride`` uint64 words apart, B int32
+        mask_of entries); ordered after the work queued on ``stream``, which is idle on return."""
+        if D:
+            n_rows = self.size()[0]
+            if int(mask_stride) * 64 < n_rows:
+                raise ValueError(f"row mask has {int(mask_stride)} words, the index {n_rows} rows "
+                                 f"(needs {(n_rows + 63) // 64})")
+        _check(self.lib.hr_index_search_masks_device(self._h, ctypes.c_void_p(q_ptr), int(B), int(k),
+                                                     ctypes.c_void_p(masks_ptr or None), int(D), int(mask_stride),
+                                                     ctypes.c_void_p(mask_of_ptr), ctypes.c_void_p(scores_ptr),
+                                                     ctypes.c_void_p(rows_ptr), ctypes.c_void_p(stream or None)))
+
+    def qmask_launches(self) -> int:
+        """FILTER launches that ran with per-query masks (one per chunk of up to 64 queries of search_masks)."""
+        out = ctypes.c_int64(0)
+        _check(self.lib.hr_index_qmask_launches(self._h, ctypes.byref(out)))
+        return int(out.value)
+
+    def set_qmask_timing(self, on: bool) -> None:
+        _check(self.lib.hr_index_set_qmask_timing(self._h, int(bool(on))))
+
+    def qmask_last_ms(self) -> dict:
+        """HIP-event times of the most recent timed search_masks call's mask prep (set_qmask_timing)."""
+        out = (ctypes.c_double * 2)()
+        _check(self.lib.hr_index_qmask_last_ms(self._h, out))
+        return {"union_tile_list_ms": out[0], "allow_table_ms": out[1]}
 
     def _mask_words(self, mask):
         if mask is None:

@@ -72,14 +72,16 @@ class _FusedRetrieve:
         # included), and cohorts finalized with no next cohort queued behind them (pipeline bubbles)
         self.timing = {"encode": 0.0, "submit": 0.0, "finalize": 0.0, "bubbles": 0}
 
-    def submit(self, query: str, top_k: int, threshold: float) -> asyncio.Future:
+    def submit(self, query: str, top_k: int, threshold: float, filters=None) -> asyncio.Future:
+        """Queue one call; `filters` (a mixed_filters store only): the call's where-clause -- the cohort's search then
+        runs as one per-query-mask call through the synchronous device path."""
         loop = asyncio.get_running_loop()
         fut = loop.create_future()
         with self._qlock:
             c = self._queues.get(loop)
             if c is None:
                 c = self._queues[loop] = _Cohort()
-        c.pending.append((query, int(top_k), float(threshold), fut))
+        c.pending.append((query, int(top_k), float(threshold), fut, filters or None))
         if not c.running:
             c.running = True
             loop.call_soon(self._form, c, loop)
@@ -102,9 +104,13 @@ class _FusedRetrieve:
                 self._thread.start()
 
     # ---- worker thread
-    def _search(self, q):
-        """Launch the cohort's search (store lock held by the caller).  Returns a finisher -> (raw, tables)."""
+    def _search(self, q, filters=None):
+        """Launch the cohort's search (store lock held by the caller).  Returns a finisher -> (raw, tables).
+        `filters`: one where-clause or None per query when some call of the cohort carries one."""
         store = self.r.vector_store
+        if filters is not None:  # per-query masks: the synchronous device path (never the pipelined submit)
+            ran = store.search_masks_device_sync(q, self._k, filters)
+            return lambda: ran
         tables = (store._records, store._metas, store._epoch)
         idx, n_live = store._index, store.count_sync()
         B, k = q.shape[0], self._k
@@ -145,7 +151,7 @@ class _FusedRetrieve:
                                                             RetrievalResult)
             except Exception as e:  # noqa: BLE001
                 exc = e
-        for i, (_, kq, th, f) in enumerate(batch):
+        for i, (_, kq, th, f, _flt) in enumerate(batch):
             if f.done():
                 continue
             if exc is not None:
@@ -190,7 +196,8 @@ class _FusedRetrieve:
                     if not locked:
                         store._lock.acquire()
                         locked = True
-                    nxt = (loop, batch, self._search(q))
+                    flt = [e[4] for e in batch]
+                    nxt = (loop, batch, self._search(q, flt if any(flt) else None))
                     tm["encode"] += t1 - t0
                     tm["submit"] += time.perf_counter() - t1
                 except Exception as e:  # noqa: BLE001 -- this cohort's callers see the failure
@@ -274,7 +281,13 @@ class VectorRetriever(BaseRetriever):
         top_k = top_k or self.config.top_k
         threshold = kwargs.get("similarity_threshold", self.config.similarity_threshold)
         collapse = bool(kwargs.get("collapse", False))
-        if self._fused is not None and not kwargs.get("filters") and self.reranker is None and not collapse:
+        filters = kwargs.get("filters")
+        # filtered calls stay in the cohort on a mixed_filters store (one forward, one per-query-mask search)
+        mixed = bool(filters) and isinstance(filters, dict) and getattr(self.vector_store, "mixed_filters", False) \
+            and callable(getattr(self.vector_store, "search_masks_device_sync", None))
+        if self._fused is not None and (not filters or mixed) and self.reranker is None and not collapse:
+            if mixed:
+                return await self._fused.submit(query, top_k, threshold, filters)
             return await self._fused.submit(query, top_k, threshold)
         qv = await self.embedder.embed_query(query)
         extra = {"collapse": True} if collapse else {}  # (off: the reference's call, for any store)

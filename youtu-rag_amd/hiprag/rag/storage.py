@@ -169,7 +169,8 @@ class _ObjColumn:
 
 
 class _SearchBatcher:
-    """Coalesces concurrent ``search`` calls into batched launches (one per filter group).
+    """Coalesces concurrent ``search`` calls into batched launches (one per filter group; with
+    ``index_params.mixed_filters`` one launch takes plain queries of any filters, each with its own row mask).
 
     Up to ``depth`` launches are in flight, and the Chunk objects of a finished batch are assembled on the
     event-loop thread while the next launch runs.  An unfiltered batch on a single-device index is launched
@@ -232,11 +233,25 @@ class _SearchBatcher:
 
     def _take(self):
         key = self.pending[0][3]
+        # mixed_filters: a launch of plain queries fills across filter keys (the batch then carries one filter per
+        # query, HipVectorStore._run_mixed); collapsed queries keep one launch per filter group and never share a
+        # launch with plain ones.  The rule is unconditional: the per-query-mask call beat one launch per filter at
+        # every point of the sweep (2 to 64 filters, 0.1 % to 30 % of the rows each, 1M and 10M rows: CHANGELOG.md);
+        # a launch whose queries share one filter takes the single-mask search (_prep_search)
+        mixed = self.store.mixed_filters and not self.pending[0][5]
         batch, rest = [], []
         for e in self.pending:
-            (batch if e[3] == key and len(batch) < self.max_batch else rest).append(e)
+            same = (not e[5]) if mixed else e[3] == key
+            (batch if same and len(batch) < self.max_batch else rest).append(e)
         self.pending = rest
         return batch
+
+    @staticmethod
+    def _batch_filters(batch):
+        """The filters of a batch: the one where-clause its queries share, else one per query."""
+        if all(e[3] == batch[0][3] for e in batch):
+            return batch[0][2]
+        return [e[2] for e in batch]
 
     @staticmethod
     def _fail(batch, exc):
@@ -304,7 +319,7 @@ class _SearchBatcher:
                         qs = np.stack([e[0] for e in batch])
                         k = max(e[1] for e in batch)
                         self.launches += 1
-                        prep = self.store._prep_search(qs, k, batch[0][2], collapse=batch[0][5])
+                        prep = self.store._prep_search(qs, k, self._batch_filters(batch), collapse=batch[0][5])
                         aw, info = self._launch(loop, prep)
                     except Exception as exc:  # noqa: BLE001 -- this batch's waiters see the failure
                         self._fail(batch, exc)
@@ -396,6 +411,11 @@ class HipVectorStore(BaseVectorStore):
         self._batcher = _SearchBatcher(self, int(params.get("max_batch", 64)), int(params.get("search_depth", 2)))
         # unfiltered batches launched from the event loop through the asynchronous native entry point
         self.native_async = bool(params.get("native_async", True))
+        # mixed-filter batches: the micro-batcher fills a launch across filter keys and the index answers it with
+        # per-query row masks in one exact scan (NativeIndex.search_masks); off: one launch per filter group
+        self.mixed_filters = bool(params.get("mixed_filters", False))
+        self.mixed_launches = 0   # diagnostics: batches answered by one per-query-mask call
+        self.grouped_launches = 0  # ... per-filter launches of list-form batches the index could not take at once
         self._lock = threading.RLock()
         self._paths = P.Paths(config.persist_directory, config.collection_name)
         self._gen = 0
@@ -853,9 +873,13 @@ class HipVectorStore(BaseVectorStore):
             return self._raw[np.asarray(rows, np.int64)]
         return self._index.get_rows(rows)
 
-    def search_batch(self, query_embeddings, top_k: int = 5, filters: dict[str, Any] | None = None, *,
+    def search_batch(self, query_embeddings, top_k: int = 5,
+                     filters: dict[str, Any] | list[dict[str, Any] | None] | None = None, *,
                      collapse: bool = False) -> list[list[tuple[Chunk, float]]]:
         """Batched search: one GPU launch for all queries (BatchedVectorRetriever, the micro-batcher).
+        ``filters``: one where-clause for every query, or a list with one where-clause or None per query (a length
+        other than the number of queries raises ValueError) -- answered by one per-query-mask scan where the index
+        has one (a single-device exact index), else by one launch per distinct filter; the results are the same.
         ``collapse=True``: one hit per group (collapse_field), the best chunk of each of the top_k best groups."""
         prep = self._prep_search(query_embeddings, top_k, filters, collapse=collapse)
         return self._assemble(prep, self._run_search(prep))
@@ -894,6 +918,13 @@ class HipVectorStore(BaseVectorStore):
         dim = self.dim
         if dim is not None and q.shape[1] != dim:
             raise ValueError(f"query dim {q.shape[1]} != collection dim {dim}")
+        if isinstance(filters, (list, tuple)):  # one where-clause (or None) per query
+            filters = list(filters)
+            if len(filters) != q.shape[0]:
+                raise ValueError(f"{len(filters)} filters for {q.shape[0]} queries")
+            keys = {_filter_key(f) for f in filters}
+            if len(keys) == 1:  # one predicate for the whole batch: the single-mask search
+                filters = filters[0] or None
         return (q, int(top_k), filters, True) if collapse else (q, int(top_k), filters)
 
     def _run_collapsed(self, q, top_k: int, filters, n_live: int):
@@ -908,6 +939,66 @@ class HipVectorStore(BaseVectorStore):
         self._ensure_groups()  # under the same lock hold as the search
         return idx.search_collapsed(q, min(top_k, n_live), self.filter_bitmap(filters))
 
+    def _distinct_filters(self, filters: list):
+        """(clauses, clause_of, bitmaps) of a per-query filter list: its distinct where-clauses in first-use order
+        (None = no filter), each query's clause, and the clauses' row bitmaps through the filter cache."""
+        order: dict[str, int] = {}
+        clauses, clause_of = [], np.empty(len(filters), np.int32)
+        for i, f in enumerate(filters):
+            key = _filter_key(f)
+            if key not in order:
+                order[key] = len(clauses)
+                clauses.append(f or None)
+            clause_of[i] = order[key]
+        return clauses, clause_of, [self.filter_bitmap(f) for f in clauses]
+
+    @staticmethod
+    def _stack_bitmaps(bitmaps: list, clause_of):
+        """(masks, mask_of) for search_masks: the bitmaps that exist stacked into one (D, words) uint64 array and, per
+        query, its row of that array (-1 for a query without a filter)."""
+        slot, rows = np.full(len(bitmaps), -1, np.int32), []
+        for c, bm in enumerate(bitmaps):
+            if bm is not None:
+                slot[c] = len(rows)
+                rows.append(np.ascontiguousarray(bm, np.uint64).reshape(-1))
+        stacked = np.zeros((len(rows), max((len(r) for r in rows), default=0)), np.uint64)
+        for j, r in enumerate(rows):
+            stacked[j, : len(r)] = r
+        return stacked, slot[clause_of]
+
+    def _takes_masks(self, idx) -> bool:
+        """The index answers per-query masks in one call: a single-device exact index with search_masks."""
+        return hasattr(idx, "search_masks") and not self.ivf and len(getattr(idx, "devices", (0,))) == 1
+
+    def _run_mixed(self, q, top_k: int, filters: list, n_live: int, collapse: bool):
+        """A batch with one where-clause (or None) per query (store lock held, rows present).  Distinct predicates
+        resolve to bitmaps through the filter cache; a single-device exact index answers the batch with ONE
+        per-query-mask call (NativeIndex.search_masks).  Multi-device handles, IVF_FLAT stores and collapsed batches
+        keep one launch per distinct filter, scattered back in query order -- the same results."""
+        idx = self._index
+        k = min(top_k, n_live)
+        clauses, mask_of, bitmaps = self._distinct_filters(filters)
+        if not collapse and self._takes_masks(idx):
+            try:
+                out = idx.search_masks(q, k, *self._stack_bitmaps(bitmaps, mask_of))
+                self.mixed_launches += 1
+                return out
+            except NotImplementedError:
+                pass  # (a handle that cannot take per-query masks: group below)
+        if collapse and top_k > _native.HR_MAX_K:
+            raise ValueError(f"a collapsed search returns at most {_native.HR_MAX_K} groups (top_k = {top_k})")
+        scores = np.full((len(filters), k), -np.inf, np.float32)
+        rows_out = np.full((len(filters), k), -1, np.int64)
+        for c, f in enumerate(clauses):
+            sel = np.nonzero(mask_of == c)[0]
+            if collapse:
+                s, r = self._run_collapsed(q[sel], top_k, f, n_live)
+            else:
+                s, r = idx.search(q[sel], k, bitmaps[c])
+            self.grouped_launches += 1
+            scores[sel, : s.shape[1]], rows_out[sel, : r.shape[1]] = s, r
+        return scores, rows_out
+
     def _run_search(self, prep):
         """The native search, under the store lock.  Everything that depends on the collection's
         current state -- the live row count, the filter bitmap (sized to the index's rows NOW, not when
@@ -919,6 +1010,8 @@ class HipVectorStore(BaseVectorStore):
             n_live = self.count_sync()
             if self._index is None or n_live == 0 or top_k <= 0:
                 return None, tables
+            if isinstance(filters, list):
+                return self._run_mixed(q, top_k, filters, n_live, len(prep) > 3 and prep[3]), tables
             if len(prep) > 3 and prep[3]:
                 return self._run_collapsed(q, top_k, filters, n_live), tables
             # top_k beyond the live rows returns them all (Chroma/FAISS); beyond HR_MAX_K the native
@@ -953,6 +1046,44 @@ class HipVectorStore(BaseVectorStore):
             st = torch.cuda.current_stream(q.device)
             idx.search_device(q.data_ptr(), B, k, s_out.data_ptr(), r_out.data_ptr(), stream=st.cuda_stream)
             host = out.cpu().numpy()  # (after the search, on the same stream)
+            return (host[:B * k].reshape(B, k).copy(), host[ns:].view(np.int64).reshape(B, k).copy()), tables
+
+    def search_masks_device_sync(self, q, top_k: int, filters: list):
+        """search_device_sync for queries that carry one where-clause (or None) each: (raw, tables) of ONE
+        per-query-mask search of the device queries in `q` (the fused retrieve on a mixed_filters store).  The bitmaps
+        go up once per call; an index without the device entry point, a multi-device handle or k beyond HR_MAX_K gets
+        a host copy of the queries through _run_mixed."""
+        import torch
+
+        if q.dim() != 2 or (self.dim is not None and q.shape[1] != self.dim):
+            raise ValueError(f"queries must be (B, {self.dim})")
+        if len(filters) != q.shape[0]:
+            raise ValueError(f"{len(filters)} filters for {q.shape[0]} queries")
+        with self._lock:  # ordered against mutations, as _run_search
+            tables = (self._records, self._metas, self._epoch)
+            n_live = self.count_sync()
+            idx = self._index
+            if idx is None or n_live == 0 or top_k <= 0:
+                return None, tables
+            k = min(int(top_k), n_live)
+            if (not q.is_cuda or not hasattr(idx, "search_masks_device") or k > _native.HR_MAX_K
+                    or not self._takes_masks(idx)):
+                return self._run_mixed(q.detach().cpu().numpy(), int(top_k), list(filters), n_live, False), tables
+            _, clause_of, bitmaps = self._distinct_filters(list(filters))
+            masks, mask_of = self._stack_bitmaps(bitmaps, clause_of)
+            q = q.to(torch.float32).contiguous()
+            B = q.shape[0]
+            m_dev = torch.from_numpy(masks.view(np.int64)).to(q.device) if masks.size else None
+            of_dev = torch.from_numpy(np.ascontiguousarray(mask_of, np.int32)).to(q.device)
+            ns = (B * k + 1) // 2 * 2
+            out = torch.empty((ns + 2 * B * k,), dtype=torch.float32, device=q.device)
+            s_out, r_out = out[:B * k], out[ns:].view(torch.int64)
+            st = torch.cuda.current_stream(q.device)
+            idx.search_masks_device(q.data_ptr(), B, k, s_out.data_ptr(), r_out.data_ptr(),
+                                    m_dev.data_ptr() if m_dev is not None else 0, masks.shape[0], masks.shape[1],
+                                    of_dev.data_ptr(), stream=st.cuda_stream)
+            self.mixed_launches += 1
+            host = out.cpu().numpy()
             return (host[:B * k].reshape(B, k).copy(), host[ns:].view(np.int64).reshape(B, k).copy()), tables
 
     def _submit_native(self, prep, batcher: _SearchBatcher, loop):
