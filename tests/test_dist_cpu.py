@@ -11,6 +11,8 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+from merge_ref import ref_merge_sorted
+
 N, DIM, B, K, KC = 3000, 96, 12, 10, 32
 
 
@@ -302,16 +304,7 @@ def _ties_queries():
 
 def _numpy_merge_sorted(cand_all, G, Bq, m, k):
     """Reference semantics of k_merge_sorted: the top-k of the union of the ranks' sorted lists."""
-    c = cand_all.numpy().reshape(G, Bq, m, 2)
-    rows_all = c.view(np.int64)[..., 1]
-    s_out = np.full((Bq, k), -np.inf, np.float32)
-    r_out = np.full((Bq, k), -1, np.int64)
-    for q in range(Bq):
-        sc, rw = c[:, q, :, 0].reshape(-1), rows_all[:, q, :].reshape(-1)
-        sc, rw = sc[rw >= 0], rw[rw >= 0]
-        order = np.lexsort((rw, -sc))[:k]
-        s_out[q, :len(order)], r_out[q, :len(order)] = sc[order], rw[order]
-    return s_out, r_out
+    return ref_merge_sorted(cand_all.numpy().reshape(G, Bq, m, 2), k)
 
 
 def _ties_worker(rank, world, port, result_path):
