@@ -565,6 +565,15 @@ static const int kSampleMin = knob("HIPRAG_SAMPLE_MIN", 1024);
 static const int kDynPct = knob("HIPRAG_DYN_PCT", 10);
 static const int kRefreshEvery = std::max(0, knob("HIPRAG_REFRESH_EVERY", 0));
 static int refresh_every(int64_t n_tiles) { return kRefreshEvery ? kRefreshEvery : (n_tiles <= 160 * 1024 ? 8 : 4); }
+// The shadow-8 FILTER refreshes every 16 tiles.  Its refreshes are synchronous (scan_body: no early refresh for the
+// I8S body) and its kc8 means four or five row parts, so each one is np memory round trips behind a drained ring:
+// at 10M x 1024 (B = 64, k = 10, np = 4) the HR_DIAG builds put 0.49 ms of the 2.18 ms launch on the refreshes after
+// the first, and the 4-tile cadence tuned for the 16-bit scan measured 2.173 ms/step against 2.019 / 1.956 / 1.939
+// at 8 / 16 / 32 tiles, no guard fallback at any (profiles/shadow8_i8_diag.jsonl).  16 rather than 32: a wave of the
+// smallest shard mode 1 scans this way (5.1M rows, 89 tiles per wave) still refreshes five times.
+// HIPRAG_REFRESH_EVERY8 overrides (HIPRAG_REFRESH_EVERY, if set, holds for every scan)
+static const int kRefreshEvery8 = std::max(0, knob("HIPRAG_REFRESH_EVERY8", 0));
+static int refresh_every8() { return kRefreshEvery8 ? kRefreshEvery8 : (kRefreshEvery ? kRefreshEvery : 16); }
 
 struct Plan {
     int QB, Bp, P;
@@ -1433,7 +1442,7 @@ static int shard_chunk(hr_index* h, const float* q_dev, int B, int kc, int kj, c
     // positions, not tiles) parts keep contiguous per-wave ranges, as does the SAMPLE pass.
     a.strided = 1;
     a.teams = tl_ptr ? 0 : 1;
-    a.refresh_every = refresh_every(n_tiles);
+    a.refresh_every = use8 ? refresh_every8() : refresh_every(n_tiles);
     // refresh loads issued before the tile's k-loop (ScanArgs::early_refresh): on small shards (the dual
     // FILTER streams' range, <= 5.1M rows) 1.25M rows 0.425 -> 0.421 ms/step; at 10M rows 2.99-3.03 ->
     // 3.05-3.07 ms (two alternating repeats on one box), so big shards keep the epilogue loads ...
