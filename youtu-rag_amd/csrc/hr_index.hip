@@ -570,10 +570,16 @@ static int refresh_every(int64_t n_tiles) { return kRefreshEvery ? kRefreshEvery
 // at 10M x 1024 (B = 64, k = 10, np = 4) the HR_DIAG builds put 0.49 ms of the 2.18 ms launch on the refreshes after
 // the first, and the 4-tile cadence tuned for the 16-bit scan measured 2.173 ms/step against 2.019 / 1.956 / 1.939
 // at 8 / 16 / 32 tiles, no guard fallback at any (profiles/shadow8_i8_diag.jsonl).  16 rather than 32: a wave of the
-// smallest shard mode 1 scans this way (5.1M rows, 89 tiles per wave) still refreshes five times.
+// smallest shard mode 1 scans this way (5.1M rows, 89 tiles per wave) still refreshes five times.  With the shared
+// refresh (HIPRAG_REFRESH_LDS, below) a refresh is one round trip and 16 stays the best: 1.963 / 1.943 / 1.935 / 1.940
+// ms/step at 4 / 8 / 16 / 32 tiles (profiles/shadow8_ldsrefresh_ab.jsonl).
 // HIPRAG_REFRESH_EVERY8 overrides (HIPRAG_REFRESH_EVERY, if set, holds for every scan)
 static const int kRefreshEvery8 = std::max(0, knob("HIPRAG_REFRESH_EVERY8", 0));
 static int refresh_every8() { return kRefreshEvery8 ? kRefreshEvery8 : (kRefreshEvery ? kRefreshEvery : 16); }
+// HIPRAG_REFRESH_LDS (1): the shadow-8 FILTER's waves share their thresholds through a row in LDS, each refreshing a
+// slice of it (scan_body: slice_apply); 0: every wave refreshes all its thresholds from the table, as the 16-bit
+// scans do (A/B runs; also what a plan whose query tile fills the LDS gets)
+static const int kRefreshLds = knob("HIPRAG_REFRESH_LDS", 1);
 
 struct Plan {
     int QB, Bp, P;
@@ -636,10 +642,10 @@ static void set_dyn_tail(ScanArgs& args, int64_t W, uint32_t* dyn_q) {
     }
 }
 
-template <int MT, int DT, int QB, int P, int MODE, bool NT, int TPB = kScanThreads, bool QM = false>
+template <int MT, int DT, int QB, int P, int MODE, bool NT, int TPB = kScanThreads, bool QM = false, bool THL = false>
 static int launch_scan_t(hr_index* h, Scratch& sc, int cus, const ScanArgs& a, hipStream_t st, int lds) {
     const int ng = std::max(1, a.ng);
-    auto kern = scan_kernel<MT, DT, QB, P, MODE, NT, TPB, QM>();
+    auto kern = scan_kernel<MT, DT, QB, P, MODE, NT, TPB, QM, THL>();
     static std::mutex attr_mu;
     static int attr_lds[64] = {};     // per device: largest dynamic LDS already allowed
     static int occ[64][4] = {};       // per device: blocks/CU for lds buckets (0 = unknown), per instantiation
@@ -807,7 +813,7 @@ static int launch_scan(hr_index* h, Scratch& sc, int cus, const Plan& pl, const 
 // the shadow-8 SAMPLE / 64-query FILTER (XFrag<F16, I8S>): f16 queries whatever the stored dtype, a ring of P8
 // 16-byte loads (each a pair of k-steps), P8 the deepest of 16 / 8 / 4 / 2 dividing S / 2.  One query group only.
 template <int MODE>
-static int launch_scan8(hr_index* h, Scratch& sc, int cus, const Plan& pl, const ScanArgs& a, hipStream_t st) {
+static int launch_scan8(hr_index* h, Scratch& sc, int cus, const Plan& pl, const ScanArgs& a_, hipStream_t st) {
     static_assert(MODE == SCAN_SAMPLE || MODE == SCAN_FILTER, "the collect pass reads the 16-bit rows");
     int lds = scan_lds_bytes(h, pl.QB);
     if (MODE == SCAN_SAMPLE) lds = std::max(lds, (kScanThreads / 64) * pl.QB * 16 * 64 * 4 + 64);
@@ -815,8 +821,21 @@ static int launch_scan8(hr_index* h, Scratch& sc, int cus, const Plan& pl, const
     const int P8 = S8 % 16 == 0 ? 16 : (S8 % 8 == 0 ? 8 : (S8 % 4 == 0 ? 4 : 2));
     constexpr bool NT = MODE == SCAN_FILTER;  // (the SAMPLE's tiles are the same every batch: default policy, as above)
     if (MODE == SCAN_FILTER) h->n_shadow8++;
-#define HR_SCAN8_CASE(QBv, Pv) \
-    if (pl.QB == QBv && P8 == Pv) return launch_scan_t<F16, I8S, QBv, Pv, MODE, NT>(h, sc, cus, a, st, lds);
+    // FILTER: the shared threshold row (ScanArgs::th_off), QB*32 floats behind the query tile where they fit (D = 1280
+    // at QB = 2 fills the 160 KiB) and the plan has at most the five row parts a slice is loaded for
+    ScanArgs a = a_;
+    a.th_off = 0;
+    if (MODE == SCAN_FILTER && kRefreshLds && a.use_groups && a.np <= 5 && lds + pl.QB * 32 * 4 <= 160 * 1024) {
+        a.th_off = lds;
+        lds += pl.QB * 32 * 4;
+    }
+#define HR_SCAN8_CASE(QBv, Pv)                                                                                      \
+    if (pl.QB == QBv && P8 == Pv) {                                                                                 \
+        if constexpr (MODE == SCAN_FILTER)                                                                          \
+            if (a.th_off)                                                                                           \
+                return launch_scan_t<F16, I8S, QBv, Pv, MODE, NT, kScanThreads, false, true>(h, sc, cus, a, st, lds); \
+        return launch_scan_t<F16, I8S, QBv, Pv, MODE, NT>(h, sc, cus, a, st, lds);                                  \
+    }
     HR_SCAN8_CASE(2, 16) HR_SCAN8_CASE(1, 16) HR_SCAN8_CASE(2, 8) HR_SCAN8_CASE(1, 8) HR_SCAN8_CASE(2, 4)
     HR_SCAN8_CASE(1, 4) HR_SCAN8_CASE(2, 2) HR_SCAN8_CASE(1, 2)
 #undef HR_SCAN8_CASE

@@ -294,6 +294,10 @@ struct ScanArgs {
     // 8-bit shadow scans (DT == I8S): fp32 scale per row, [tile * 32 + row % 32]; the accumulators are multiplied
     // by the lane's row scale before the threshold compare, the group maxima and the append
     const float* rscale;
+    // shadow-8 FILTER: byte offset in LDS (behind the query tile) of the workgroup's shared threshold row, QB*32
+    // floats -- each wave refreshes a slice of it and all read it (scan_body: th_row).  0: off, every wave
+    // refreshes all its thresholds from the table itself
+    int th_off;
 };
 
 
@@ -512,8 +516,12 @@ enum { SCAN_SAMPLE = 0, SCAN_FILTER = 1, SCAN_COLLECT = 2 };
 // body needs a few of its own, and this body is at the 256-VGPR limit with SGPRs spilled to VGPR lanes).
 // QM (SAMPLE / FILTER of a batch with per-query row masks): the live / mask word shared by the 64 queries gives way
 // to the lane's allow word (ScanArgs::mask, read as the allow table), one bit per accumulator register.
-template <int MT, int DT, int QB, int P, int MODE, bool NT, int TPB, bool LEAN = false, bool QM = false>
+// THL (the shadow-8 FILTER where its threshold row fits in LDS, ScanArgs::th_off): the shared refresh (slice_apply below)
+// instead of the per-wave one.  A kernel of its own: with both refreshes in one body the old one's 64 key registers
+// shape the register allocation of the whole tile loop.
+template <int MT, int DT, int QB, int P, int MODE, bool NT, int TPB, bool LEAN = false, bool QM = false, bool THL = false>
 __device__ __forceinline__ void scan_body(ScanArgs a) {
+    static_assert(!THL || (DT == I8S && !LEAN && !QM && MODE == SCAN_FILTER), "the shared refresh: the shadow-8 FILTER");
     constexpr bool FILTER = MODE != SCAN_SAMPLE;
     constexpr bool priv = MODE == SCAN_FILTER;
     static_assert(!LEAN || MODE == SCAN_FILTER, "the lean body is a FILTER");
@@ -654,6 +662,13 @@ __device__ __forceinline__ void scan_body(ScanArgs a) {
         if (ring0) __builtin_amdgcn_s_waitcnt(vmcnt_only(P * XFrag<MT, DT, NT>::kLoads));
         else __builtin_amdgcn_s_waitcnt(vmcnt_only(0));
     }
+    // The shadow-8 FILTER's shared threshold row (ScanArgs::th_off): QB*32 floats behind the query tile, -inf until
+    // a wave's slice refresh (below) writes a query's threshold.
+    constexpr bool TH_ROW = THL;
+    float* const th_row = (float*)(lds + (TH_ROW ? a.th_off : 0));
+    if constexpr (TH_ROW) {
+        if (tid < QB * 32) th_row[tid] = -__builtin_inff();
+    }
     __syncthreads();
 
     if (u0 >= u1 && FILTER) {
@@ -782,6 +797,83 @@ __device__ __forceinline__ void scan_body(ScanArgs a) {
     };
     if (FILTER) refresh(false);
 
+    // Shared refresh (THL).  After refresh_apply's lane reduction a threshold depends only on
+    // its query -- min over the 32*np (part, group) keys, max'd with the floor -- yet each of the workgroup's 8 waves
+    // loaded all 32*np keys of all QB*32 queries for it: np dependent round trips of 16*QB loads behind a drained ring,
+    // then 16*QB five-step lane reductions.  Here a wave fetches one eighth of the table per refresh -- slice s: 2*SW
+    // consecutive queries, one SW-word load per lane per part, all parts in one round trip, 32/SW lanes to a query --
+    // reduces it with log2(32/SW) shuffles, writes those queries' thresholds to the LDS row and then raises its own
+    // thresholds to the row's (16*QB/4 16-byte LDS reads).  Wave v takes slice (v + r) % NSL at its r-th refresh, so a
+    // wave that runs out of units strands no query.  No barrier: a slot is one 32-bit word and every value ever
+    // written is the min over a snapshot of the table (keys only rise), so never above what k_select computes from
+    // the final table; a stale slot only lets a few more candidates through.
+    // Publishing needs no loaded key: a group maximum goes out where it beats the wave's own threshold.  th is never
+    // above the current min over groups, so a value <= th cannot lift that min above th -- withholding it loses
+    // nothing a later threshold could use -- and the table stays a set of true scores of rows of their groups, which
+    // is all k_select's thr and bound_approx need.
+    // The slice is loaded here in the epilogue, behind the next tile's ring refills (one drain per refresh): held
+    // across the k-loop instead, even one word per lane per part spilled (7 / 19 / 26 VGPRs at 1 / 2 / 4 words).
+    constexpr int SW = 2 * QB;  // words per lane per part (QB = 1: half the queries, half the words)
+    constexpr int NSL = QB * 32 / (2 * SW);
+    constexpr int kThParts = 5;  // row parts of the deepest shadow-8 plan (the host turns the row off beyond)
+    int th_r = tid >> 6;  // wave index + refreshes done
+    [[maybe_unused]] auto slice_apply = [&]() {
+        const int s = __builtin_amdgcn_readfirstlane(th_r % NSL);
+        ++th_r;
+        // (lane-derived LDS and buffer offsets are formed here: hoisted out of the tile loop they are held across the
+        // k-loop, where this body has no register to spare)
+        int ln = lane;
+        asm volatile("" : "+v"(ln));
+        // sc1 (aux 16): served by L2 like the relaxed agent-scope loads above -- a plain load may hit this CU's L1,
+        // which no other CU's atomics ever refresh
+        const __amdgpu_buffer_rsrc_t kr =
+            __builtin_amdgcn_make_buffer_rsrc((void*)a.mkeys, (short)0, (int)(a.np * a.pstride * 4), 0x00020000);
+        uint32_t sl[kThParts][SW];
+#pragma unroll
+        for (int p = 0; p < kThParts; ++p) {
+            const int pp = p < a.np ? p : a.np - 1;  // (a part read twice leaves the minimum as it is)
+            const int soff = (int)(pp * a.pstride + s * (64 * SW)) * 4;
+            if constexpr (SW == 4) {
+                const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(kr, ln * 16, soff, 16);
+                sl[p][0] = v.x, sl[p][1] = v.y, sl[p][2] = v.z, sl[p][3] = v.w;
+            } else if constexpr (SW == 2) {
+                const auto v = __builtin_amdgcn_raw_buffer_load_b64(kr, ln * 8, soff, 16);
+                sl[p][0] = v[0], sl[p][1] = v[1];
+            } else {
+                sl[p][0] = __builtin_amdgcn_raw_buffer_load_b32(kr, ln * 4, soff, 16);
+            }
+        }
+        if (a.publish) {
+#pragma unroll
+            for (int qb = 0; qb < QB; ++qb)
+#pragma unroll
+                for (int i = 0; i < 16; ++i)
+                    if (gmax[qb][i] > th[qb][i])  // (result unused: an atomic without return, nothing to wait for)
+                        atomicMax(gkq[qb] + 32 * ((i & 3) + 8 * (i >> 2)), f2key(gmax[qb][i]));
+        }
+        uint32_t m = sl[0][0];
+#pragma unroll
+        for (int p = 0; p < kThParts; ++p)
+#pragma unroll
+            for (int j = 0; j < SW; ++j) m = m < sl[p][j] ? m : sl[p][j];
+        float f = key2f(m > HR_KEY_NEG_INF ? m : HR_KEY_NEG_INF);
+#pragma unroll
+        for (int off = 32 / SW / 2; off >= 1; off >>= 1) f = fminf(f, __shfl_xor(f, off, 64));
+        if ((ln & (32 / SW - 1)) == 0) th_row[s * (2 * SW) + ln / (32 / SW)] = f;
+        asm volatile("" ::: "memory");  // the row is read afresh at every refresh (other waves write it)
+#pragma unroll
+        for (int qb = 0; qb < QB; ++qb)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {  // acc_query(qb, 4 j + c, half) = qb*32 + 8 j + 4 half + c: one 16-byte read
+                typedef float f32x4 __attribute__((ext_vector_type(4)));
+                const f32x4 r = *(const f32x4*)(th_row + qb * 32 + 8 * j + 4 * (ln >> 5));
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    th[qb][4 * j + c] = fmaxf(th[qb][4 * j + c], r[c]);
+                    gmax[qb][4 * j + c] = -__builtin_inff();
+                }
+            }
+    };
 
     // grab the next dynamic run: first unit, or -1 when the pool is exhausted
     // The grab is issued one unit before its result is needed (runs are >= 2 units long): the
@@ -1000,7 +1092,8 @@ __device__ __forceinline__ void scan_body(ScanArgs a) {
 #undef HR_OKR
         ++done;
         if (MODE == SCAN_FILTER && !(HR_DIAG & 2) && ((done + roff) % a.refresh_every) == 0) {
-            if (rdue) refresh_apply(rkey, true, false);
+            if constexpr (TH_ROW) slice_apply();  // (launched with use_groups only: launch_scan8)
+            else if (rdue) refresh_apply(rkey, true, false);
             else refresh(true);
         }
         if (u + 1 < u_end) {
@@ -1073,13 +1166,22 @@ template <int MT, int DT, int QB, int P, bool NT, int TPB, bool QM = false>
 __global__ __launch_bounds__(TPB, TPB >= 512 ? 2 : 1) void k_scan_filter(ScanArgs a) {
     scan_body<MT, DT, QB, P, SCAN_FILTER, NT, TPB, false, QM>(a);
 }
+// the shadow-8 FILTER with the shared threshold refresh (scan_body: THL): the same kernel name in a namespace of its
+// own, so profiles and the resource checks see it as a k_scan_filter and tell it from the per-wave one
+namespace lds_refresh {
+template <int MT, int DT, int QB, int P, bool NT, int TPB>
+__global__ __launch_bounds__(TPB, TPB >= 512 ? 2 : 1) void k_scan_filter(ScanArgs a) {
+    scan_body<MT, DT, QB, P, SCAN_FILTER, NT, TPB, false, false, true>(a);
+}
+}  // namespace lds_refresh
 template <int MT, int DT, int QB, int P, bool NT, int TPB>
 __global__ __launch_bounds__(TPB, TPB >= 512 ? 2 : 1) void k_scan_collect(ScanArgs a) {
     scan_body<MT, DT, QB, P, SCAN_COLLECT, NT, TPB>(a);
 }
-template <int MT, int DT, int QB, int P, int MODE, bool NT, int TPB, bool QM = false>
+template <int MT, int DT, int QB, int P, int MODE, bool NT, int TPB, bool QM = false, bool THL = false>
 constexpr auto scan_kernel() {
     if constexpr (MODE == SCAN_SAMPLE) return &k_scan_sample<MT, DT, QB, P, NT, TPB, QM>;
+    else if constexpr (MODE == SCAN_FILTER && THL) return &lds_refresh::k_scan_filter<MT, DT, QB, P, NT, TPB>;
     else if constexpr (MODE == SCAN_FILTER) return &k_scan_filter<MT, DT, QB, P, NT, TPB, QM>;
     else return &k_scan_collect<MT, DT, QB, P, NT, TPB>;
 }
