@@ -183,6 +183,32 @@ int hr_index_search_collapsed(hr_index* h, const float* q, int B, int k, int pro
 int hr_index_search_collapsed_device(hr_index* h, const float* q_dev, int B, int k, int probe,
                                      const uint64_t* row_mask_dev, float* scores_out_dev, int64_t* rows_out_dev,
                                      void* stream);
+/* MMR search: k rows per query chosen by maximal marginal relevance -- relevant rows that do not repeat each other
+ * (LangChain's max_marginal_relevance_search) -- on the device, bit for bit restatable (tests/mmr_ref.py).
+ * Pool: the exact top-P of hr_index_search(h, q, B, P, row_mask), P = fetch_k, in its order (canonical score desc,
+ * row asc; live, allowed rows only; slots with row -1 are padding and never candidates).  rel[j] = the fp32 score of
+ * pool position j, widened to double.
+ * Similarity: sim(s, j) = the canonical fp64 score, under the index's metric, of stored row j against a QUERY whose
+ * components are stored row s widened to fp32 (lane-strided fp64 accumulation over the padded dim, the butterfly
+ * sum, and for l2 1 - ((|s|^2 - 2 s.j) + |j|^2)), read from the stored rows.  The selected row always takes the
+ * query role: for l2 on fp32 rows sim(s, j) and sim(j, s) can differ in the last bit.
+ * Greedy selection: step 0 takes position 0.  maxsim[j] = the fp64 max of sim(s, j) over the rows s selected so
+ * far.  Every further step takes the unselected candidate with the largest
+ *     v[j] = lambda * rel[j] - (1 - lambda) * maxsim[j]
+ * -- two products and a subtraction, each rounded once, no fused multiply-add, 1 - lambda computed once; a NaN v[j]
+ * counts as -inf; ties go to the lowest pool position.  It stops after min(k, candidates in the pool) picks.
+ * Output: the rows in SELECTION order, each with its fp32 relevance rel (what hr_index_search returns for it, so a
+ * score threshold keeps its meaning); the scores are therefore NOT monotone down the list.  Remaining slots
+ * -inf / -1.  lambda = 1 is hr_index_search's top-k; for a fixed fetch_k and lambda the k'-pick answer is the
+ * first k' entries of the k-pick answer.  The pool is exact and the answer a function of it: no fallback stage.
+ * Limits: 1 <= k <= fetch_k <= HR_MAX_K; fetch_k = 0: the default min(HR_MAX_K, max(32, 4 k)); lambda outside
+ * [0, 1] or NaN: HR_E_INVALID; a multi-device handle: HR_E_UNSUPPORTED; an empty index returns padding.  The
+ * device form is ordered after the work queued on `stream` and returns with it idle. */
+int hr_index_search_mmr(hr_index* h, const float* q, int B, int k, int fetch_k, double lambda,
+                        const uint64_t* row_mask, float* scores_out, int64_t* rows_out);
+int hr_index_search_mmr_device(hr_index* h, const float* q_dev, int B, int k, int fetch_k, double lambda,
+                               const uint64_t* row_mask_dev, float* scores_out_dev, int64_t* rows_out_dev,
+                               void* stream);
 int hr_index_size(hr_index* h, int64_t* n_out, int64_t* n_live_out);
 /* Shape of a handle (e.g. one returned by hr_index_load): dim, storage dtype, metric, devices. */
 int hr_index_info(hr_index* h, int* dim_out, int* dtype_out, int* metric_out, int* n_dev_out);

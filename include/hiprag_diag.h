@@ -75,6 +75,12 @@ int hr_index_collapse_stats(hr_index* h, int64_t out[2]);
 int hr_index_set_collapse_timing(hr_index* h, int on);
 int hr_index_collapse_last_ms(hr_index* h, double out[3]);
 
+/* Diagnostics of the MMR search (hr_index_search_mmr): set_mmr_timing(h, 1) records HIP events around the two stages
+ * of every MMR call; mmr_last_ms then reports the most recent call's probe search (out[0]) and selection kernel
+ * (out[1]), in ms.  Off by default. */
+int hr_index_set_mmr_timing(hr_index* h, int on);
+int hr_index_mmr_last_ms(hr_index* h, double out[2]);
+
 /* Diagnostics of the pipelined search: out[0] = caller host time per submit (us), out[1] = host time
  * per batch of the busiest shard thread (us), out[2] = batches submitted. */
 int hr_index_host_us(hr_index* h, double* out);

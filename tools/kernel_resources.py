@@ -21,7 +21,8 @@ TARGET = "hipv4-amdgcn-amd-amdhsa--gfx950"
 
 
 def kernel_resources(lib: str) -> dict[str, dict]:
-    """{kernel symbol: {"vgpr_count", "vgpr_spill_count", "sgpr_spill_count", "agpr_count"}} over every bundle."""
+    """{kernel symbol: {"vgpr_count", "vgpr_spill_count", "sgpr_spill_count", "agpr_count",
+    "private_segment_fixed_size", "group_segment_fixed_size"}} over every bundle."""
     out: dict[str, dict] = {}
     with tempfile.TemporaryDirectory() as td:
         sec = os.path.join(td, "fatbin")
@@ -39,14 +40,18 @@ def kernel_resources(lib: str) -> dict[str, dict]:
                 continue
             notes = subprocess.run([f"{LLVM}/llvm-readelf", "--notes", co], check=True, capture_output=True,
                                    text=True).stdout
-            cur = None
+            cur, lds = None, None
             for line in notes.splitlines():
                 m = re.match(r"\s*-?\s*\.(\w+):\s+(\S+)", line)
                 if not m:
                     continue
                 key, val = m.groups()
-                if key == "name" and not val.endswith(".kd"):
+                if key == "group_segment_fixed_size":  # static LDS bytes; a kernel's keys are sorted, so this one
+                    lds = int(val)                     # comes before the .name it belongs to
+                elif key == "name" and not val.endswith(".kd"):
                     cur = out.setdefault(val, {})
+                    if lds is not None:
+                        cur["group_segment_fixed_size"], lds = lds, None
                 elif cur is not None and key in ("vgpr_count", "vgpr_spill_count", "sgpr_spill_count", "agpr_count",
                                                      "private_segment_fixed_size"):
                     cur[key] = int(val)

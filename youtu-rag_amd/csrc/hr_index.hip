@@ -2812,6 +2812,7 @@ extern "C" void hr_index_destroy(hr_index* h) {
     if (h->xnorm) (void)hipFree(h->xnorm);
     if (h->norm_bits) (void)hipFree(h->norm_bits);
     collapse_free(h);
+    mmr_free(h);
     (void)hipDeviceSynchronize();  // pipelined batches may still run on caller streams
     for (auto& g : h->sync_graphs)
         if (g.exec) (void)hipGraphExecDestroy(g.exec);

@@ -297,6 +297,11 @@ struct hr_index {
     bool collapse_timing = false;     // hr_index_set_collapse_timing: HIP events around the stages of every call
     hipEvent_t col_ev[4] = {nullptr, nullptr, nullptr, nullptr};
     double col_ms[3] = {0.0, 0.0, 0.0};  // probe search, prefix kernel, stage 2 of the most recent timed call
+    // ---- MMR search (hr_mmr.hip): the probe's pool and the host form's staging; allocated by the first call
+    DevBuf mmr_q, mmr_mask, mmr_s, mmr_r, mmr_out;  // host queries / mask, pool scores / rows, host results
+    bool mmr_timing = false;          // hr_index_set_mmr_timing: HIP events around the two stages of every call
+    hipEvent_t mmr_ev[3] = {nullptr, nullptr, nullptr};
+    double mmr_ms[2] = {0.0, 0.0};    // probe search, selection kernel of the most recent timed call
 };
 
 // an internal stream of h: on h's CU mask when one is set (priority is then not available), else high priority or
@@ -358,6 +363,7 @@ int index_search_locked(hr_index* h, const float* q_dev, int B, int k, const uin
 int index_prep_exact(hr_index* h, const float* q_dev, int B, hipStream_t st, const float** q32_out,
                      std::vector<double>* qerr_out);
 void collapse_free(hr_index* h);
+void mmr_free(hr_index* h);  // hr_mmr.hip: hr_index_destroy's part
 int launch_merge(int device, const Cand* cand, const double* bounds, int G, int B, int kc, int k, float* s_out,
                  int64_t* r_out, double* kth_out, int32_t* fail_out, hipStream_t st, int64_t cstride = 0,
                  int64_t bstride = 0);

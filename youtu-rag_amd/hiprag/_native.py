@@ -60,6 +60,7 @@ EXPORTS = [
     "hr_index_collapse_stats", "hr_index_set_collapse_timing", "hr_index_collapse_last_ms",
     "hr_index_search_masks", "hr_index_search_masks_device", "hr_index_qmask_launches",
     "hr_index_set_qmask_timing", "hr_index_qmask_last_ms",
+    "hr_index_search_mmr", "hr_index_search_mmr_device", "hr_index_set_mmr_timing", "hr_index_mmr_last_ms",
 ]
 
 _lib = None
@@ -213,6 +214,10 @@ def load_library(path: str | None = None):
             "hr_index_qmask_launches": [vp, vp],
             "hr_index_set_qmask_timing": [vp, i32],
             "hr_index_qmask_last_ms": [vp, vp],
+            "hr_index_search_mmr": [vp, vp, i32, i32, i32, ctypes.c_double, vp, vp, vp],
+            "hr_index_search_mmr_device": [vp, vp, i32, i32, i32, ctypes.c_double, vp, vp, vp, vp],
+            "hr_index_set_mmr_timing": [vp, i32],
+            "hr_index_mmr_last_ms": [vp, vp],
         }
         for name, args in sig.items():
             if p != (path or LIB_PATH) and not hasattr(L, name):
@@ -501,6 +506,43 @@ class NativeIndex:
         out = (ctypes.c_double * 3)()
         _check(self.lib.hr_index_collapse_last_ms(self._h, out))
         return {"probe_ms": out[0], "prefix_ms": out[1], "all_rows_ms": out[2]}
+
+    # -- MMR search (hr_mmr.hip): k rows chosen by maximal marginal relevance from the exact top-fetch_k pool
+    def search_mmr(self, q: np.ndarray, k: int, lam: float, mask: np.ndarray | None = None,
+                   fetch_k: int = 0) -> tuple[np.ndarray, np.ndarray]:
+        """search() diversified (hr_index_search_mmr): greedy picks of the largest lam * relevance - (1 - lam) * (max
+        similarity to the rows picked so far) from the exact top-``fetch_k`` (0 = min(HR_MAX_K, max(32, 4 k))).  Rows
+        in selection order, each with its plain-search score: the scores are not monotone.  lam = 1 is search()."""
+        q = np.ascontiguousarray(q, np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.shape[1] != self.dim:
+            raise ValueError(f"query dim {q.shape[1]} != index dim {self.dim}")
+        B = q.shape[0]
+        if int(k) <= 0 or int(k) > HR_MAX_K:  # (before the output arrays are sized by it)
+            raise ValueError(f"k must be in [1, {HR_MAX_K}]")
+        s = np.empty((B, int(k)), np.float32)
+        r = np.empty((B, int(k)), np.int64)
+        m = self._mask_words(mask)
+        _check(self.lib.hr_index_search_mmr(self._h, _ptr(q), B, int(k), int(fetch_k), float(lam), _ptr(m), _ptr(s),
+                                            _ptr(r)))
+        return s, r
+
+    def search_mmr_device(self, q_ptr: int, B: int, k: int, lam: float, scores_ptr: int, rows_ptr: int,
+                          mask_ptr: int = 0, fetch_k: int = 0, stream: int = 0) -> None:
+        _check(self.lib.hr_index_search_mmr_device(self._h, ctypes.c_void_p(q_ptr), int(B), int(k), int(fetch_k),
+                                                   float(lam), ctypes.c_void_p(mask_ptr or None),
+                                                   ctypes.c_void_p(scores_ptr), ctypes.c_void_p(rows_ptr),
+                                                   ctypes.c_void_p(stream or None)))
+
+    def set_mmr_timing(self, on: bool) -> None:
+        _check(self.lib.hr_index_set_mmr_timing(self._h, int(bool(on))))
+
+    def mmr_last_ms(self) -> dict:
+        """HIP-event times of the most recent timed MMR call (set_mmr_timing)."""
+        out = (ctypes.c_double * 2)()
+        _check(self.lib.hr_index_mmr_last_ms(self._h, out))
+        return {"probe_ms": out[0], "select_ms": out[1]}
 
     def search_device(self, q_ptr: int, B: int, k: int, scores_ptr: int, rows_ptr: int, mask_ptr: int = 0,
                       stream: int = 0) -> None:

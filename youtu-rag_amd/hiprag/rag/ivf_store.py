@@ -209,6 +209,10 @@ class IvfStoreIndex:
     def collapse_stats(self) -> dict:
         return self.exact.collapse_stats()
 
+    # MMR search is always exact too: its pool is the exact top-fetch_k, so the exact index answers
+    def search_mmr(self, q: np.ndarray, k: int, lam: float, mask: np.ndarray | None = None, fetch_k: int = 0):
+        return self.exact.search_mmr(q, k, lam, mask, fetch_k)
+
     # ---------------------------------------------------------------- persistence
     def save(self, path: str) -> None:
         """The exact index to ``path`` as ever, and ``path + ".ivf.npz"``: centroids, nlist, the seed, the list of

@@ -22,6 +22,8 @@ same error shape.
 One addition, off by default: ``config["collapse_files"]`` makes ``kb_file_search`` ask the store for distinct files
 (a collapsed search by ``source``) instead of de-duplicating an over-fetch on the host, which returns
 fewer than ``top_k`` files whenever one file owns most of the fetched rows (kb_search_toolkit.py:539-568).
+Another, off by default too: ``config["mmr_lambda"]`` (in [0, 1], with an optional ``config["mmr_fetch_k"]``) makes
+``kb_embedding_search`` return a diversified list -- the store's MMR search -- in selection order.
 """
 from __future__ import annotations
 
@@ -136,6 +138,9 @@ class KBSearchToolkit(BaseRAGToolkit):
         self.reranker_config = c.get("reranker", {})
         # kb_file_search through the store's collapsed search: the fetched rows are distinct files already
         self.collapse_files = bool(c.get("collapse_files", False))
+        # kb_embedding_search through the store's MMR search (None: the plain ranking)
+        self.mmr_lambda = None if c.get("mmr_lambda") is None else float(c["mmr_lambda"])
+        self.mmr_fetch_k = None if c.get("mmr_fetch_k") is None else int(c["mmr_fetch_k"])
         self.reranker = self._init_reranker()
 
     def _init_reranker(self):
@@ -177,7 +182,11 @@ class KBSearchToolkit(BaseRAGToolkit):
             retrieval_top_k = top_k * self.recall_multiplier if auto_rerank else top_k
             filters = self._build_metadata_filters(metadata_filters)
             retriever = await self._create_retriever(kb_id, retrieval_top_k)
-            results = await retriever.retrieve(query=query, filters=filters)
+            if self.mmr_lambda is not None:  # diversified hits (the store's MMR search)
+                results = await retriever.retrieve(query=query, filters=filters, mmr_lambda=self.mmr_lambda,
+                                                   fetch_k=self.mmr_fetch_k)
+            else:
+                results = await retriever.retrieve(query=query, filters=filters)
             out = {"kb_id": kb_id, "query": query, "total_results": len(results), "top_k": top_k,
                    "filters_applied": metadata_filters if metadata_filters else None,
                    "results": [self._row(r) for r in results]}

@@ -12,6 +12,9 @@ VectorRetriever keeps the reference's semantics exactly
 ``collapse=True`` in the kwargs (no counterpart in the reference) asks the store for one hit per group -- the best chunk
 of each of the best documents (HipVectorStore, ``collapse_field``); threshold, ranks and the ``2*top_k`` fetch under a
 reranker apply to the collapsed list as to the plain one.
+``mmr_lambda=`` (with an optional ``fetch_k=``) in the kwargs asks the store for a diversified list instead (maximal
+marginal relevance, HipVectorStore.search_batch): the hits arrive in selection order with their plain-search scores, and
+threshold, ranks and the ``2*top_k`` fetch under a reranker apply to that list in the same way.
 BatchedVectorRetriever overrides batch_retrieve (the reference's loop at :95-98)
 with one query-embedding batch and one GPU search launch for the whole batch,
 producing the same per-query results.
@@ -277,10 +280,21 @@ class VectorRetriever(BaseRetriever):
             results = await self.reranker.rerank(query=query, results=results, top_k=top_k)
         return results[:top_k]
 
+    @staticmethod
+    def _mode_kwargs(kwargs) -> dict:
+        """The store keywords of a collapsed or MMR call (empty: the reference's call, for any store)."""
+        extra = {"collapse": True} if kwargs.get("collapse", False) else {}
+        if kwargs.get("mmr_lambda") is not None:
+            extra["mmr_lambda"] = kwargs["mmr_lambda"]
+            if kwargs.get("fetch_k") is not None:
+                extra["fetch_k"] = kwargs["fetch_k"]
+        return extra
+
     async def retrieve(self, query: str, top_k: int | None = None, **kwargs) -> list[RetrievalResult]:
         top_k = top_k or self.config.top_k
         threshold = kwargs.get("similarity_threshold", self.config.similarity_threshold)
-        collapse = bool(kwargs.get("collapse", False))
+        extra = self._mode_kwargs(kwargs)
+        collapse = bool(extra)  # collapsed and MMR calls bypass the fused cohort path
         filters = kwargs.get("filters")
         # filtered calls stay in the cohort on a mixed_filters store (one forward, one per-query-mask search)
         mixed = bool(filters) and isinstance(filters, dict) and getattr(self.vector_store, "mixed_filters", False) \
@@ -290,7 +304,6 @@ class VectorRetriever(BaseRetriever):
                 return await self._fused.submit(query, top_k, threshold, filters)
             return await self._fused.submit(query, top_k, threshold)
         qv = await self.embedder.embed_query(query)
-        extra = {"collapse": True} if collapse else {}  # (off: the reference's call, for any store)
         hits = await self.vector_store.search(query_embedding=qv, top_k=top_k * 2 if self.reranker else top_k,
                                               filters=kwargs.get("filters"), **extra)
         return await self._finish(query, self._to_results(hits, threshold), top_k)
@@ -315,7 +328,7 @@ class BatchedVectorRetriever(VectorRetriever):
         threshold = kwargs.get("similarity_threshold", self.config.similarity_threshold)
         embed_many = getattr(self.embedder, "embed_queries", None)
         qvs = await embed_many(queries) if embed_many else [await self.embedder.embed_query(q) for q in queries]
-        extra = {"collapse": True} if kwargs.get("collapse", False) else {}
+        extra = self._mode_kwargs(kwargs)
         hits = search_batch(qvs, top_k * 2 if self.reranker else top_k, kwargs.get("filters"), **extra)
         results = [self._to_results(h, threshold) for h in hits]
         rerank_batch = getattr(self.reranker, "rerank_batch", None)
@@ -395,6 +408,9 @@ class HybridRetriever(BaseRetriever):
         if kwargs.get("collapse", False):
             raise ValueError("HybridRetriever does not fuse collapsed lists: collapse=True needs a store without an "
                              "active keyword search, or VectorRetriever")
+        if kwargs.get("mmr_lambda") is not None:
+            raise ValueError("HybridRetriever does not fuse MMR lists: mmr_lambda needs a store without an active "
+                             "keyword search, or VectorRetriever")
         if not queries:
             return []
         top_k = top_k or self.config.top_k

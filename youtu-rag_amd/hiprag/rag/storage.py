@@ -53,6 +53,12 @@ that field names; a row without that key groups by its document_id, as kb_file_s
 (type, value): 1, 1.0 and True stay apart) and a host int32 column are built at the first collapsed search and
 extended by every add; nothing of them is persisted.
 
+MMR search (``search(..., mmr_lambda=0.5)`` / ``search_batch(..., mmr_lambda=0.5)``, optional ``fetch_k``; single
+device): ``top_k`` hits that are relevant but do not repeat each other, chosen on the GPU by maximal marginal relevance
+from the exact top-``fetch_k`` (hr_index_search_mmr).  The hits come in selection order with their
+plain-search scores, so the scores are not monotone.  Concurrent MMR queries of one (lambda, fetch_k, filter) share a
+launch whatever their ``top_k``.  Not combined with ``collapse``.
+
 ``index_type: "IVF_FLAT"`` (any letter case; single device, cosine / dot): the index is an ``IvfStoreIndex``
 (ivf_store.py) -- the same exact index plus an IVF replica that answers searches once ``ivf_train_rows`` live rows
 are stored (``index_params``: nlist, nprobe, ivf_train_rows = 64 nlist, ivf_seed).  It comes in through the
@@ -179,7 +185,7 @@ class _SearchBatcher:
     as a count on an eventfd the loop watches (written by a host function behind the batch's results), so
     no Python thread takes part -- no GIL hand-off between a worker and the loop per launch.  Filtered
     batches, multi-device handles, and launches that find the handle or the store busy run the blocking
-    search in a worker thread (``asyncio.to_thread``; ctypes drops the GIL), and so do collapsed batches."""
+    search in a worker thread (``asyncio.to_thread``; ctypes drops the GIL), and so do collapsed and MMR batches."""
 
     def __init__(self, store: "HipVectorStore", max_batch: int, depth: int = 2):
         self.store, self.max_batch, self.depth = store, max(1, int(max_batch)), max(1, int(depth))
@@ -193,7 +199,8 @@ class _SearchBatcher:
         self._drain_loop = None   # the loop the running drain belongs to
         self._inflight: dict = {}  # the running drain's launches: awaitable -> (batch, prep, native info or None)
 
-    def submit(self, q: np.ndarray, top_k: int, filters, collapse: bool = False) -> asyncio.Future:
+    def submit(self, q: np.ndarray, top_k: int, filters, collapse: bool = False, mmr: tuple | None = None
+               ) -> asyncio.Future:
         """Queue one query; the future resolves to its (Chunk, score) list.  A plain call, not a coroutine: the
         caller's own coroutine awaits the future, so a query in flight holds one coroutine frame fewer for the
         cycle collector to walk and promote (the store's event loop is collector-bound under load)."""
@@ -206,7 +213,13 @@ class _SearchBatcher:
         fut = loop.create_future()
         # collapsed and plain queries never share a launch: the flag is part of the group key
         key = _filter_key(filters)
-        self.pending.append((q, int(top_k), filters, "collapse\0" + key if collapse else key, fut, bool(collapse)))
+        if mmr is not None:
+            # MMR queries (mmr = ("mmr", lambda, fetch_k), _mmr_mode) share a launch with MMR queries of the same
+            # lambda, pool size and filter only -- of any top_k: a k'-pick answer is the prefix of the k-pick one, so
+            # the launch runs at the batch's largest top_k and _drain cuts each query's list to its own
+            self.pending.append((q, int(top_k), filters, ("mmr", mmr[1], mmr[2], key), fut, mmr))
+        else:
+            self.pending.append((q, int(top_k), filters, "collapse\0" + key if collapse else key, fut, bool(collapse)))
         if not self.running:
             self.running, self._drain_loop = True, loop
             # start draining on the next loop iteration: every task that is ready now enqueues first
@@ -234,8 +247,8 @@ class _SearchBatcher:
     def _take(self):
         key = self.pending[0][3]
         # mixed_filters: a launch of plain queries fills across filter keys (the batch then carries one filter per
-        # query, HipVectorStore._run_mixed); collapsed queries keep one launch per filter group and never share a
-        # launch with plain ones.  The rule is unconditional: the per-query-mask call beat one launch per filter at
+        # query, HipVectorStore._run_mixed); collapsed and MMR queries keep one launch per filter group and never share
+        # a launch with plain ones or with each other.  The rule is unconditional: the per-query-mask call beat one launch per filter at
         # every point of the sweep (2 to 64 filters, 0.1 % to 30 % of the rows each, 1M and 10M rows: CHANGELOG.md);
         # a launch whose queries share one filter takes the single-mask search (_prep_search)
         mixed = self.store.mixed_filters and not self.pending[0][5]
@@ -319,7 +332,11 @@ class _SearchBatcher:
                         qs = np.stack([e[0] for e in batch])
                         k = max(e[1] for e in batch)
                         self.launches += 1
-                        prep = self.store._prep_search(qs, k, self._batch_filters(batch), collapse=batch[0][5])
+                        mode = batch[0][5]  # False, True (collapsed) or the MMR mode tuple
+                        if isinstance(mode, tuple):
+                            prep = self.store._prep_search(qs, k, self._batch_filters(batch), mmr=mode)
+                        else:
+                            prep = self.store._prep_search(qs, k, self._batch_filters(batch), collapse=mode)
                         aw, info = self._launch(loop, prep)
                     except Exception as exc:  # noqa: BLE001 -- this batch's waiters see the failure
                         self._fail(batch, exc)
@@ -875,14 +892,42 @@ class HipVectorStore(BaseVectorStore):
 
     def search_batch(self, query_embeddings, top_k: int = 5,
                      filters: dict[str, Any] | list[dict[str, Any] | None] | None = None, *,
-                     collapse: bool = False) -> list[list[tuple[Chunk, float]]]:
+                     collapse: bool = False, mmr_lambda: float | None = None,
+                     fetch_k: int | None = None) -> list[list[tuple[Chunk, float]]]:
         """Batched search: one GPU launch for all queries (BatchedVectorRetriever, the micro-batcher).
         ``filters``: one where-clause for every query, or a list with one where-clause or None per query (a length
         other than the number of queries raises ValueError) -- answered by one per-query-mask scan where the index
         has one (a single-device exact index), else by one launch per distinct filter; the results are the same.
-        ``collapse=True``: one hit per group (collapse_field), the best chunk of each of the top_k best groups."""
-        prep = self._prep_search(query_embeddings, top_k, filters, collapse=collapse)
+        ``collapse=True``: one hit per group (collapse_field), the best chunk of each of the top_k best groups.
+        ``mmr_lambda`` in [0, 1]: a diversified list (maximal marginal relevance) -- top_k greedy picks
+        of the largest mmr_lambda * score - (1 - mmr_lambda) * (similarity to the hits picked so far) from the exact
+        top-``fetch_k`` (default min(HR_MAX_K, max(32, 4 top_k))).  The hits come in selection order, each with its
+        plain-search score: the scores are not monotone down the list.  Not combined with ``collapse``; ``fetch_k``
+        without ``mmr_lambda`` means nothing."""
+        mmr = self._mmr_mode(top_k, mmr_lambda, fetch_k, collapse)
+        if mmr is not None:
+            prep = self._prep_search(query_embeddings, top_k, filters, mmr=mmr)
+        else:
+            prep = self._prep_search(query_embeddings, top_k, filters, collapse=collapse)
         return self._assemble(prep, self._run_search(prep))
+
+    @staticmethod
+    def _mmr_mode(top_k: int, mmr_lambda, fetch_k, collapse: bool):
+        """None for a search without ``mmr_lambda``, else its checked mode ("mmr", lambda, pool size): every limit of
+        hr_index_search_mmr is checked here, before a query is queued, so a bad one fails alone."""
+        if mmr_lambda is None:
+            return None
+        if collapse:
+            raise ValueError("mmr_lambda and collapse=True do not combine")
+        lam, k, top = float(mmr_lambda), int(top_k), _native.HR_MAX_K
+        if not 0.0 <= lam <= 1.0:  # (NaN fails both comparisons)
+            raise ValueError(f"mmr_lambda must be in [0, 1] (got {mmr_lambda})")
+        if k > top:
+            raise ValueError(f"an MMR search returns at most {top} hits (top_k = {top_k})")
+        pool = min(top, max(32, 4 * k)) if fetch_k is None else int(fetch_k)
+        if pool < max(k, 1) or pool > top:
+            raise ValueError(f"fetch_k must be in [top_k, {top}] (got {fetch_k}, top_k = {top_k})")
+        return ("mmr", lam, pool)
 
     def keyword_search_batch(self, queries: list[str], top_k: int = 5, filters: dict[str, Any] | None = None
                              ) -> list[list[tuple[Chunk, float]]]:
@@ -911,7 +956,9 @@ class HipVectorStore(BaseVectorStore):
     # search_batch in three steps, so the micro-batcher can run only the middle one in a worker thread
     # (it holds the GIL for little but the ctypes call; a worker doing the Python parts was starved by
     # a busy event loop) and assemble on the event-loop thread while the next launch runs
-    def _prep_search(self, query_embeddings, top_k: int, filters, collapse: bool = False):
+    def _prep_search(self, query_embeddings, top_k: int, filters, collapse: bool = False, mmr: tuple | None = None):
+        """(q, top_k, filters) of a plain search; a fourth entry carries another mode: True = collapsed, the
+        ("mmr", lambda, pool size) tuple of _mmr_mode = MMR."""
         q = np.asarray(query_embeddings, dtype=np.float32)
         if q.ndim == 1:
             q = q[None, :]
@@ -925,7 +972,18 @@ class HipVectorStore(BaseVectorStore):
             keys = {_filter_key(f) for f in filters}
             if len(keys) == 1:  # one predicate for the whole batch: the single-mask search
                 filters = filters[0] or None
+        if mmr is not None:
+            return (q, int(top_k), filters, mmr)
         return (q, int(top_k), filters, True) if collapse else (q, int(top_k), filters)
+
+    def _run_mmr(self, q, top_k: int, filters, n_live: int, mmr: tuple):
+        """The native MMR search (store lock held, rows present); mmr: the checked mode of _mmr_mode."""
+        idx = self._index
+        if len(getattr(idx, "devices", (0,))) > 1:
+            raise ValueError("an MMR search needs a single-device store")
+        if not hasattr(idx, "search_mmr"):
+            raise NotImplementedError(f"{type(idx).__name__} has no MMR search")
+        return idx.search_mmr(q, min(top_k, n_live), mmr[1], self.filter_bitmap(filters), mmr[2])
 
     def _run_collapsed(self, q, top_k: int, filters, n_live: int):
         """The collapsed native search (store lock held, rows present)."""
@@ -974,11 +1032,14 @@ class HipVectorStore(BaseVectorStore):
         """A batch with one where-clause (or None) per query (store lock held, rows present).  Distinct predicates
         resolve to bitmaps through the filter cache; a single-device exact index answers the batch with ONE
         per-query-mask call (NativeIndex.search_masks).  Multi-device handles, IVF_FLAT stores and collapsed batches
-        keep one launch per distinct filter, scattered back in query order -- the same results."""
+        keep one launch per distinct filter, scattered back in query order -- the same results -- and so do MMR
+        batches (collapse: False, True, or the MMR mode tuple)."""
         idx = self._index
         k = min(top_k, n_live)
         clauses, mask_of, bitmaps = self._distinct_filters(filters)
-        if not collapse and self._takes_masks(idx):
+        mmr = collapse if isinstance(collapse, tuple) else None
+        collapse = collapse is True
+        if not collapse and mmr is None and self._takes_masks(idx):
             try:
                 out = idx.search_masks(q, k, *self._stack_bitmaps(bitmaps, mask_of))
                 self.mixed_launches += 1
@@ -993,6 +1054,8 @@ class HipVectorStore(BaseVectorStore):
             sel = np.nonzero(mask_of == c)[0]
             if collapse:
                 s, r = self._run_collapsed(q[sel], top_k, f, n_live)
+            elif mmr is not None:
+                s, r = self._run_mmr(q[sel], top_k, f, n_live, mmr)
             else:
                 s, r = idx.search(q[sel], k, bitmaps[c])
             self.grouped_launches += 1
@@ -1012,6 +1075,8 @@ class HipVectorStore(BaseVectorStore):
                 return None, tables
             if isinstance(filters, list):
                 return self._run_mixed(q, top_k, filters, n_live, len(prep) > 3 and prep[3]), tables
+            if len(prep) > 3 and isinstance(prep[3], tuple):
+                return self._run_mmr(q, top_k, filters, n_live, prep[3]), tables
             if len(prep) > 3 and prep[3]:
                 return self._run_collapsed(q, top_k, filters, n_live), tables
             # top_k beyond the live rows returns them all (Chroma/FAISS); beyond HR_MAX_K the native
@@ -1090,7 +1155,7 @@ class HipVectorStore(BaseVectorStore):
         """Launch an unfiltered batch through the asynchronous native entry point from the event loop
         (None: this batch takes the worker-thread path -- a filter, no async-capable index, k beyond
         HR_MAX_K, an empty collection, or the store / handle busy: nothing here ever waits)."""
-        if len(prep) > 3 and prep[3]:  # collapsed: the worker-thread route, as filtered batches
+        if len(prep) > 3 and prep[3]:  # collapsed or MMR: the worker-thread route, as filtered batches
             return None
         q, top_k, filters = prep
         idx = self._index
@@ -1187,10 +1252,15 @@ class HipVectorStore(BaseVectorStore):
         return fn(Chunk, result_cls, *g, [int(k) for k in ks], [float(t) for t in ths], self.untracked_results)
 
     async def search(self, query_embedding: list[float], top_k: int = 5, filters: dict[str, Any] | None = None, *,
-                     collapse: bool = False) -> list[tuple[Chunk, float]]:
+                     collapse: bool = False, mmr_lambda: float | None = None,
+                     fetch_k: int | None = None) -> list[tuple[Chunk, float]]:
+        """One query through the micro-batcher; ``collapse``, ``mmr_lambda`` and ``fetch_k`` as search_batch."""
+        mmr = self._mmr_mode(top_k, mmr_lambda, fetch_k, collapse)  # checked before queueing: a bad query fails alone
         if int(top_k) <= 0:
             return []
         q = np.asarray(query_embedding, dtype=np.float32).reshape(-1)
+        if mmr is not None:
+            return await self._batcher.submit(q, top_k, filters, mmr=mmr)
         if not collapse:
             return await self._batcher.submit(q, top_k, filters)
         if int(top_k) > _native.HR_MAX_K:  # checked before queueing: a bad query fails alone
