@@ -1022,13 +1022,19 @@ __device__ __forceinline__ void scan_body(ScanArgs a) {
 #pragma unroll
                 for (int i = 0; i < 16; ++i) acc[qb][i] = __builtin_fmaf(xmul, acc[qb][i], -xs);
         }
-        if constexpr (DT == I8S) {
+        const bool ok = (allow >> rg) & 1u;
+        // 8-bit shadow: the row scale and the predicate in one FMA.  The addend is -0.0 on an allowed lane -- x*y + (-0)
+        // has the bits of x*y whatever they are (with +0 a product of -0 would come out +0) -- and -inf on a masked,
+        // deleted or padding one, which makes the score -inf, or NaN where the product is +inf or NaN itself: the
+        // group maximum ignores both and both fail the compare.  The compare pass below is then straight-line code.
+        constexpr bool FOLD = DT == I8S;  // (never with per-query masks: the static_assert above)
+        if constexpr (FOLD) {
+            const float bias = ok ? -0.0f : -__builtin_inff();
 #pragma unroll
             for (int qb = 0; qb < QB; ++qb)
 #pragma unroll
-                for (int i = 0; i < 16; ++i) acc[qb][i] *= rsc;
+                for (int i = 0; i < 16; ++i) acc[qb][i] = __builtin_fmaf(acc[qb][i], rsc, bias);
         }
-        const bool ok = (allow >> rg) & 1u;
         // the predicate of accumulator register (qb, i): shared by the queries, or (QM) that query's bit of the allow word
 #define HR_OKR(qb, i) (QM ? ((aw >> ((qb) * 16 + (i))) & 1u) != 0 : ok)
         const uint32_t row = (uint32_t)(t * 32 + rg);
@@ -1037,21 +1043,37 @@ __device__ __forceinline__ void scan_body(ScanArgs a) {
         // ballot for all 16*QB of them: early in a scan, while the threshold is still loose, most
         // tiles append something)
         uint32_t regs = 0;
+        if constexpr (FOLD) {
+            // a forbidden lane's -inf still passes a threshold that is -inf itself: the tile's allowed lanes mask
+            // the compare (one ballot per tile; no select and no write of EXEC per register)
+            const uint64_t okm = __ballot(ok);
 #pragma unroll
-        for (int qb = 0; qb < QB; ++qb)
+            for (int qb = 0; qb < QB; ++qb)
 #pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const float v = HR_OKR(qb, i) ? acc[qb][i] : -__builtin_inff();
-                gmax[qb][i] = fmaxf(gmax[qb][i], v);
-                if (FILTER) regs |= (__ballot(HR_OKR(qb, i) && v >= th[qb][i]) != 0 ? 1u : 0u) << (qb * 16 + i);
-            }
+                for (int i = 0; i < 16; ++i) {
+                    gmax[qb][i] = fmaxf(gmax[qb][i], acc[qb][i]);
+                    if (FILTER) regs |= ((__ballot(acc[qb][i] >= th[qb][i]) & okm) != 0 ? 1u : 0u) << (qb * 16 + i);
+                }
+        } else {
+#pragma unroll
+            for (int qb = 0; qb < QB; ++qb)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const float v = HR_OKR(qb, i) ? acc[qb][i] : -__builtin_inff();
+                    gmax[qb][i] = fmaxf(gmax[qb][i], v);
+                    if (FILTER) regs |= (__ballot(HR_OKR(qb, i) && v >= th[qb][i]) != 0 ? 1u : 0u) << (qb * 16 + i);
+                }
+        }
         if (FILTER && regs && !(HR_DIAG & 1)) {
 #pragma unroll
             for (int qb = 0; qb < QB; ++qb)
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {
                     if (!((regs >> (qb * 16 + i)) & 1u)) continue;
-                    const float v = acc[qb][i];
+                    float v = acc[qb][i];
+                    // (the compare is made again here: reusing the pass above's would hold its 16*QB lane masks in
+                    // scalar registers down to this point, which spills)
+                    if constexpr (FOLD) asm volatile("" : "+v"(v));
                     const bool pass = HR_OKR(qb, i) && v >= th[qb][i];
                     const uint64_t m = __ballot(pass);
                     if (m) {
