@@ -111,7 +111,7 @@ extern "C" int hr_index_create_ex(int dim, int dtype, int metric, int n_dev, con
         hr_index_destroy(h);
         return set_err(HR_E_HIP, std::string("hr_index_create: ") + hipGetErrorString(e));
     }
-    h->n_cu = prop.multiProcessorCount;
+    h->n_cu = h->n_cu_dev = prop.multiProcessorCount;
     *out = h;
     return HR_OK;
 }
@@ -646,6 +646,25 @@ static void set_dyn_tail(ScanArgs& args, int64_t W, uint32_t* dyn_q) {
     }
 }
 
+// Private candidate slots per (wave, query) of a FILTER launch of W waves (per query group) over n_units units.
+// kCapW was sized on the whole device's grid.  The candidates a query collects do not get fewer when a CU mask
+// (hr_index_set_cu_mask) shrinks the grid -- k = 100, five row parts: ~2050 per query on 128 waves of a 16-CU mask as
+// on 2048 -- so with W_dev / W times fewer regions each one holds that many times more, up to what its wave can append
+// at all (32 rows of each tile it scans) and at most 32 x kCapW.  With 32 slots the 16-CU grid sent 1-6 of 64 queries
+// to the collect pass at k = 100, every query with query groups, over a tile list or pipelined, and 6-14 (k = 10) or
+// all (k = 40) of the shadow-8 scan's (tests/test_gpu_scan_steady_state.py).
+// Without a mask (n_cu == n_cu_dev) every launch keeps kCapW, whatever its grid.  Under a mask W_dev is the launch's
+// grid on ALL the device's CUs, so a query's slots over all regions stay within 32 x W_dev: what an unmasked
+// synchronous launch has, and n_cu_dev / (n_cu_dev - tail CUs) of what an unmasked pipelined one has (its FILTER
+// leaves the tail CUs out; 256 / 224 by default).  The persistent FILTER (persist_configure, hr_persist.hip) keeps
+// its fixed kCapW regions under a mask too.
+static int region_slots(const hr_index* h, int64_t W, int64_t W_dev, int64_t n_units) {
+    if (h->n_cu == h->n_cu_dev) return kCapW;
+    const int64_t per_wave = (n_units + W - 1) / W;
+    const int64_t scale = std::min<int64_t>({per_wave, W_dev / W, 32});
+    return kCapW * (int)std::max<int64_t>(1, scale);
+}
+
 template <int MT, int DT, int QB, int P, int MODE, bool NT, int TPB = kScanThreads, bool QM = false, bool THL = false>
 static int launch_scan_t(hr_index* h, Scratch& sc, int cus, const ScanArgs& a, hipStream_t st, int lds) {
     const int ng = std::max(1, a.ng);
@@ -678,18 +697,21 @@ static int launch_scan_t(hr_index* h, Scratch& sc, int cus, const ScanArgs& a, h
     if (MODE == SCAN_FILTER) {
         const int64_t W = blocks * (TPB / 64);  // waves per group
         const int Bq = QB * 32;
-        HIP_TRY(sc.pbuf.ensure((size_t)ng * Bq * W * kCapW * sizeof(float2)));
+        int64_t blocks_dev = std::max<int64_t>(1, (int64_t)h->n_cu_dev * per_cu / ng);  // (as `blocks`, all CUs)
+        if (ng > 1) blocks_dev = std::max<int64_t>(8, blocks_dev / 8 * 8);
+        const int capw = region_slots(h, W, blocks_dev * (TPB / 64), a.n_units);
+        HIP_TRY(sc.pbuf.ensure((size_t)ng * Bq * W * capw * sizeof(float2)));
         HIP_TRY(sc.pcnt.ensure((size_t)ng * Bq * W * 4));
         HIP_TRY(sc.wtiles.ensure((size_t)ng * W * 4));
         args.wave_tiles = sc.wtiles.as<uint32_t>();
         sc.wtiles_valid = true;
         args.pbuf = sc.pbuf.as<float2>();
         args.pcnt = sc.pcnt.as<uint32_t>();
-        args.capw = kCapW;
+        args.capw = capw;
         sc.last_W = W;
         sc.last_Bp = Bq;
         sc.last_ng = ng;
-        sc.last_capw = kCapW;
+        sc.last_capw = capw;
         h->last_scr = &sc;
         set_dyn_tail(args, W, sc.dyn_q.as<uint32_t>());
     }
@@ -719,18 +741,19 @@ static int launch_scan_p(hr_index* h, Scratch& sc, int cus, const Plan& pl, cons
             if (pl.NG == 4 && a.np == 1 && h->q256 && q256_filter_ok(scan_dtype(h), h->S)) {
                 const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(cus, (a.n_units + 7) / 8));
                 const int64_t W = (int64_t)blocks * 4;  // waves: one candidate region per (group, wave)
-                HIP_TRY(sc.pbuf.ensure((size_t)4 * 64 * W * kCapW * sizeof(float2)));
+                const int capw = region_slots(h, W, (int64_t)h->n_cu_dev * 4, a.n_units);
+                HIP_TRY(sc.pbuf.ensure((size_t)4 * 64 * W * capw * sizeof(float2)));
                 HIP_TRY(sc.pcnt.ensure((size_t)4 * 64 * W * 4));
                 sc.last_W = W;
                 sc.last_Bp = 64;
                 sc.last_ng = 4;
-                sc.last_capw = kCapW;
+                sc.last_capw = capw;
                 sc.wtiles_valid = false;
                 h->last_scr = &sc;
                 ScanArgs b = a;
                 b.pbuf = sc.pbuf.as<float2>();
                 b.pcnt = sc.pcnt.as<uint32_t>();
-                b.capw = kCapW;
+                b.capw = capw;
                 if (int rc = launch_filter_q256(MT, DT, h->S, blocks, b, st)) return set_err(rc, "256-query FILTER launch failed");
                 h->n_q256++;
                 return HR_OK;
@@ -739,12 +762,13 @@ static int launch_scan_p(hr_index* h, Scratch& sc, int cus, const Plan& pl, cons
             constexpr int wpb = 8;
             const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(cus, (a.n_units + wpb - 1) / wpb));
             const int64_t W = (int64_t)blocks * wpb;
-            HIP_TRY(sc.pbuf.ensure((size_t)pl.NG * 64 * W * kCapW * sizeof(float2)));
+            const int capw = region_slots(h, W, (int64_t)h->n_cu_dev * wpb, a.n_units);
+            HIP_TRY(sc.pbuf.ensure((size_t)pl.NG * 64 * W * capw * sizeof(float2)));
             HIP_TRY(sc.pcnt.ensure((size_t)pl.NG * 64 * W * 4));
             sc.last_W = W;
             sc.last_Bp = 64;
             sc.last_ng = pl.NG;
-            sc.last_capw = kCapW;
+            sc.last_capw = capw;
             sc.wtiles_valid = false;
             h->last_scr = &sc;
             for (int set = 0; set < pl.NG / 2; ++set) {  // two groups per launch
@@ -752,9 +776,9 @@ static int launch_scan_p(hr_index* h, Scratch& sc, int cus, const Plan& pl, cons
                 b.qfrag = a.qfrag + (int64_t)set * 2 * h->S * 2 * 64 * 8;
                 b.mkeys = a.mkeys + set * 128 * 32;
                 b.floor_q = a.floor_q + set * 128;
-                b.pbuf = sc.pbuf.as<float2>() + (int64_t)set * 2 * W * 64 * kCapW;
+                b.pbuf = sc.pbuf.as<float2>() + (int64_t)set * 2 * W * 64 * capw;
                 b.pcnt = sc.pcnt.as<uint32_t>() + (int64_t)set * 2 * W * 64;
-                b.capw = kCapW;
+                b.capw = capw;
                 if (int rc = launch_filter_wide(MT, DT, h->S, blocks, b, st)) return set_err(rc, "wide FILTER launch failed");
                 h->n_wide++;
             }

@@ -198,7 +198,8 @@ struct hr_index {
     int time_every = 0;               // record events around every Nth main pass (0 = never)
     int64_t main_passes = 0;
     bool isolate_next = false;        // dual-stream mode: the next FILTER waits for a timed one
-    int n_cu = 256;
+    int n_cu = 256;                   // CUs the grids are sized from (hr_index_set_cu_mask: the mask's)
+    int n_cu_dev = 256;               // CUs of the device, whatever the mask (region_slots)
     std::mutex mu;
     // tile list of the current selective-filter search (hr_index_search with a row mask that
     // leaves at most half the tiles): sorted tiles holding a live, allowed row; tl_n = -1: none
