@@ -107,3 +107,83 @@ def test_fused_retrieve_on_gpu_matches_two_step(tmp_path):
         assert len(g) == 8 and abs(g[0].score - w[0].score) < 2e-2
     store.close()
     ret._fused.close()
+
+
+@pytest.mark.timeout(300)
+def test_fused_retriever_cohorts_of_mixed_top_k(tmp_path):
+    """Four cohorts whose k are 10, 50, 200, 10 -- the pipelined submit, a k above the searcher's kc (32) while the
+    first cohort is in flight, a k above HR_MAX_K (the store's synchronous search, no searcher), the pipelined submit
+    again -- all queued before the worker's first forward returns (the stub embedder holds it until they are), twice
+    on one retriever.  No call raises; every call's (chunk id, score, rank) list is the unfused retriever's."""
+    import threading
+
+    from hiprag.rag import HipVectorStore, RetrieverConfig, VectorRetriever, VectorStoreConfig
+    from hiprag.rag.base import Chunk
+    from oracle import ref_numpy as R
+
+    n, dim, nq = 4_000, 64, 128
+    raw = R.gen_rows(12, 0, n, dim)
+    rng = np.random.default_rng(6)
+    names = [f"q{i}" for i in range(nq)]
+    table = {nm: (raw[rng.integers(n)] + 0.2 * rng.standard_normal(dim)).astype(np.float32) for nm in names}
+    ks = [(10, 50, 200, 10)[i // 32] for i in range(nq)]
+
+    class Emb:  # the in-process embedder's surface the fused path needs; the vectors come from the table
+        batch_size, fused_retrieve, _fwd_lock = 32, True, threading.Lock()
+        hold, entered, gate = False, threading.Event(), threading.Event()
+
+        async def embed_query(self, text):
+            return table[text].tolist()
+
+        def encode_queries(self, texts):
+            if Emb.hold:  # the first forward of a run waits until every cohort is queued behind it
+                Emb.hold = False
+                Emb.entered.set()
+                if not Emb.gate.wait(timeout=120):
+                    raise RuntimeError("the cohorts were never all queued")
+            return torch.from_numpy(np.stack([table[t] for t in texts])).to("cuda:0")
+
+    class Plain(Emb):
+        fused_retrieve = False
+
+    cfg = VectorStoreConfig(backend="hip", collection_name="mixedk", persist_directory=str(tmp_path),
+                            index_params={"persist": False})
+    store = HipVectorStore(cfg)
+    store.add_chunks_sync([Chunk(id=f"c{i}", document_id=f"d{i // 500}", content=f"text {i}", chunk_index=i % 500,
+                                 metadata={}, embedding=raw[i].tolist()) for i in range(n)])
+    rc = RetrieverConfig(top_k=5, similarity_threshold=0.0)
+    fused, plain = VectorRetriever(store, Emb(), rc), VectorRetriever(store, Plain(), rc)
+    assert fused._fused is not None and fused._fused.max_batch == 32 and plain._fused is None
+    ident = lambda res: [[(r.chunk.id, r.score, r.rank) for r in x] for x in res]  # noqa: E731
+    want = ident([asyncio.run(plain.retrieve(nm, top_k=k)) for nm, k in zip(names, ks)])
+    assert [len(w) for w in want] == ks
+    fr = fused._fused
+
+    async def go():
+        loop = asyncio.get_running_loop()
+        Emb.entered.clear()
+        Emb.gate.clear()
+        Emb.hold = True
+        all_calls = asyncio.gather(*[fused.retrieve(nm, top_k=k) for nm, k in zip(names, ks)], return_exceptions=True)
+
+        def release():  # cohort 1 is in the held forward and the other three wait in the worker's queue
+            if Emb.entered.is_set() and fr._work.qsize() == 3:
+                Emb.gate.set()
+            elif not all_calls.done():
+                loop.call_later(0.001, release)
+
+        loop.call_soon(release)
+        return await all_calls
+
+    searchers = []
+    for run in range(2):
+        got = asyncio.run(go())
+        raised = [g for g in got if isinstance(g, BaseException)]
+        assert not raised, raised[:3]
+        assert Emb.gate.is_set() and ident(got) == want
+        searchers.append(fr._searcher[1])
+    assert searchers[0] is searchers[1] and searchers[0].kc == 32  # one searcher served both runs
+    fr.close()  # (the worker counts a cohort after it has posted its results)
+    # every cohort but a run's last was finalized with its successor already submitted
+    assert fr.cohorts == 8 and fr.queries == 2 * nq and fr.pipelined == 6
+    store.close()

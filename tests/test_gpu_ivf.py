@@ -105,3 +105,83 @@ def test_ivf_ties_padding_dot_and_synthetic():
     sb, rb = b.search(qq, 10, 3)
     assert torch.equal(ra, rb) and torch.equal(sa, sb)
     assert int(ra.min()) >= 100
+
+
+def test_ivf_sharded_search_tickets_and_k_limit():
+    """hiprag.ivf.IvfShardedSearch on one GPU (no process group): search at k below and at the k it was built with,
+    two batches in flight finalized out of order, a masked search, all identical to the oracle's IVF restatement over
+    the index's own centroids and lists; nprobe = nlist is NativeIndex.search; a k above the built k is refused
+    before any work, with the batch in flight left finalizable; no fallback ever runs (bounds are -inf)."""
+    import torch
+
+    from hiprag import _native
+    from hiprag.ivf import IvfShardedSearch
+
+    rng = np.random.default_rng(23)
+    dim, n, nlist, K, nprobe = 64, 3000, 16, 40, 3
+    x = _clustered(rng, n, dim, n_centers=12)
+    ivf = _build(x, nlist, "bf16")
+    stored = R.process_rows(x, "cosine", "bf16")
+    cent = ivf.centroids[:, :dim].cpu().numpy()
+    row_list = ivf.lists_of_rows.cpu().numpy()
+
+    def queries(B):
+        j = rng.choice(n, B // 2, replace=False)
+        return np.concatenate([x[j] + 0.02 * rng.standard_normal((len(j), dim)).astype(np.float32),
+                               rng.standard_normal((B - len(j), dim)).astype(np.float32)]).astype(np.float32)
+
+    def same(got, q, k, npr=nprobe, lists=row_list):
+        s, r = got
+        s_ref, r_ref, _ = R.ivf_search(stored, "bf16", R.process_queries(q, "cosine"), cent, lists, npr, k)
+        assert tuple(r.shape) == (len(q), k)
+        np.testing.assert_array_equal(r.cpu().numpy(), r_ref)
+        np.testing.assert_array_equal(s.cpu().numpy().astype(np.float64), s_ref.astype(np.float32).astype(np.float64))
+
+    for bad in (0, 1025):
+        with pytest.raises(ValueError, match="1024"):
+            IvfShardedSearch(ivf, max_batch=32, k=bad, nprobe=nprobe)
+    ss = IvfShardedSearch(ivf, max_batch=32, k=K, nprobe=nprobe)
+    q9, q20 = queries(9), queries(20)
+    d9, d20 = torch.from_numpy(q9).cuda(), torch.from_numpy(q20).cuda()
+    for q, d in ((q9, d9), (q20, d20)):
+        for k in (10, K):
+            same(ss.search(d, k), q, k)
+    # two batches in flight, finalized out of order (and once more: a ticket keeps its answer)
+    ta, tb = ss.submit(d9, 10), ss.submit(d20, K)
+    same(ss.finalize(tb), q20, K)
+    same(ss.finalize(ta), q9, 10)
+    same(ss.finalize(tb), q20, K)
+    # k above the built k: refused before any work, what is in flight stays in flight
+    t = ss.submit(d20, 10)
+    for call in (ss.submit, ss.search):
+        with pytest.raises(ValueError, match="41"):
+            call(d9, K + 1)
+    assert t.slot is not None and t.slot.ticket is t
+    same(ss.finalize(t), q20, 10)
+    # a masked search: the by-id row bitmap as the position mask hr_ivf_search reads (kept alive until finalize)
+    allowed = rng.random(n) < 0.5
+    words = oracle.mask_from_bool(allowed)
+    md = torch.from_numpy(words.view(np.int64)).cuda()
+    pm = torch.empty((ivf.n_positions + 31) // 32, dtype=torch.int32, device="cuda")
+    _native.ivf_position_mask(ivf.ids.data_ptr(), ivf.n_positions, md.data_ptr(), len(words) * 64, pm.data_ptr(),
+                              torch.cuda.current_stream().cuda_stream)
+    tm = ss.submit(d20, K, mask_ptr=pm.data_ptr())
+    tu = ss.submit(d9, K)
+    got = ss.finalize(tm)
+    same(got, q20, K, lists=np.where(allowed, row_list, -1))
+    assert allowed[got[1].cpu().numpy()[got[1].cpu().numpy() >= 0]].all()
+    same(ss.finalize(tu), q9, K)
+    assert ss.fallback_queries == 0 and ss.exact_queries == 0
+    ss.close()
+    # every list probed: the exact search
+    full = IvfShardedSearch(ivf, max_batch=32, k=K, nprobe=nlist)
+    s, r = full.search(d20, 10)
+    flat = _native.NativeIndex(dim, "bf16", "cosine")
+    flat.add(x)
+    s_f, r_f = flat.search(q20, 10)
+    np.testing.assert_array_equal(r.cpu().numpy(), r_f)
+    np.testing.assert_array_equal(s.cpu().numpy(), s_f)
+    assert full.fallback_queries == 0
+    full.close()
+    flat.close()
+    ivf.close()

@@ -46,13 +46,29 @@ def fallback_cap(G: int) -> int:
     return max(64, min(1024, 8192 // max(1, G)))
 
 
-class _Done:
+class _Ticket:
+    """One submitted batch: the searcher it belongs to, the slot it runs in while in flight (None once finalized),
+    what its fallback needs (its own queries, k, mask, batch size) and its outputs.  The one object a submit
+    allocates; finalize drops the queries and the slot, the outputs stay for every later finalize."""
+
+    __slots__ = ("owner", "slot", "q", "k", "s_out", "r_out", "mask_ptr", "B")
+
+    def __init__(self, owner, slot, q, k, s_out, r_out, mask_ptr, B):
+        self.owner, self.slot, self.q, self.k = owner, slot, q, k
+        self.s_out, self.r_out, self.mask_ptr, self.B = s_out, r_out, mask_ptr, B
+
+    @property
+    def result(self):
+        return self.s_out, self.r_out
+
+
+class _Done(_Ticket):
     """Ticket of a batch answered inside submit (k above the pipelined kc): finalize returns its outputs."""
 
-    __slots__ = ("result",)
+    __slots__ = ()
 
-    def __init__(self, s_out, r_out):
-        self.result = (s_out, r_out)
+    def __init__(self, owner, k, s_out, r_out, B):
+        super().__init__(owner, None, None, k, s_out, r_out, 0, B)
 
 
 def _record_len(B: int, kc: int) -> int:
@@ -141,7 +157,7 @@ class _Slot:
         self.fail = torch.empty((B,), dtype=torch.int32, device=device)
         self.fail_h = torch.empty((B,), dtype=torch.int32, pin_memory=pinned)
         self.event = torch.cuda.Event() if pinned else None
-        self.ticket = None  # (q, k, s_out, r_out, mask_ptr, B) while in flight
+        self.ticket = None  # the _Ticket of the batch in flight in this slot
         self._views: dict = {}
         self._qbuf = None
         self.q_event = torch.cuda.Event() if pinned else None
@@ -320,7 +336,15 @@ class ShardedSearch:
         identical on every rank.  q_ready: optional recorded torch.cuda.Event after which q (and
         the mask) are ready; then a large shard preps the queries and runs its SAMPLE pass beside
         the previous batch's FILTER scan instead of after it.  Without it the queries are taken to
-        be ready in the current stream's order."""
+        be ready in the current stream's order.
+
+        The ticket stands for this batch alone: every batch gets its own, and finalize(ticket) returns this
+        batch's (s_out, r_out) whenever and however often it is called.  The searcher finalizes a batch itself
+        when it needs to -- finalize_all(), close(), a submit with k above the pipelined kc (answered synchronously
+        after everything in flight), or a later submit that takes this batch's slot (the depth + 1-th submit
+        after it) -- and then runs the batch's guard fallback with the batch's own queries, k and mask before the
+        slot's buffers are used again.  So the memory behind mask_ptr (and q) must stay alive and unchanged until
+        the ticket has been finalized, by the caller or by one of those calls."""
         torch = self.torch
         B = int(q.shape[0])
         k = int(k)
@@ -332,8 +356,8 @@ class ShardedSearch:
             return self._submit_beyond_kc(q, k, s_out, r_out, mask_ptr, src_rank)
         slot = self.slots[self._next]
         self._next = (self._next + 1) % len(self.slots)
-        if slot.ticket is not None:
-            self.finalize(slot)
+        if slot.ticket is not None:  # the batch that last ran here: its fallback before its buffers go
+            self.finalize(slot.ticket)
         q = q.contiguous()
         if src_rank is not None and self.collective:
             # the batch arrives on one rank: ONE broadcast (RCCL over xGMI, 4*B*dim bytes) on the scan
@@ -358,8 +382,8 @@ class ShardedSearch:
                 self._exchange_and_merge(slot, rec, L, B, k, s_out, r_out)
         else:
             self._exchange_and_merge(slot, rec, L, B, k, s_out, r_out)
-        slot.ticket = (q, k, s_out, r_out, mask_ptr, B)
-        return slot
+        slot.ticket = ticket = _Ticket(self, slot, q, k, s_out, r_out, mask_ptr, B)
+        return ticket
 
     def _exchange_and_merge(self, slot, rec, L, B, k, s_out, r_out):
         torch = self.torch
@@ -376,14 +400,19 @@ class ShardedSearch:
         else:
             slot.fail_h[:B].copy_(fail)
 
-    def finalize(self, slot) -> tuple:
-        """Wait for a submitted batch's guard flags (only those) and run its fallback if needed."""
-        if isinstance(slot, _Done):
-            return slot.result
-        if slot.ticket is None:
-            raise ValueError("ticket already finalized")
-        q, k, s_out, r_out, mask_ptr, B = slot.ticket
-        slot.ticket = None
+    def finalize(self, ticket) -> tuple:
+        """The (s_out, r_out) of the batch `ticket` was returned for by this searcher's submit -- that batch's and
+        no other's, on every call.  The first finalize of a batch in flight waits for its guard flags (only those)
+        and runs its fallback if needed; a batch already finalized -- by an earlier call, by finalize_all(),
+        close(), a submit above the pipelined kc or the submit that took its slot -- and a batch answered inside
+        submit return their outputs at once.  Anything that is not a ticket of this searcher: ValueError."""
+        if not isinstance(ticket, _Ticket) or ticket.owner is not self:
+            raise ValueError("not a ticket of this searcher's submit")
+        slot = ticket.slot
+        if slot is None:
+            return ticket.s_out, ticket.r_out
+        q, k, s_out, r_out, mask_ptr, B = ticket.q, ticket.k, ticket.s_out, ticket.r_out, ticket.mask_ptr, ticket.B
+        ticket.slot = ticket.q = slot.ticket = None
         if slot.event is not None:
             t0 = time.perf_counter()
             slot.event.synchronize()
@@ -409,10 +438,11 @@ class ShardedSearch:
             self.rccl = None
 
     def finalize_all(self):
+        """Finalize every batch in flight, oldest first (their tickets stay good for finalize)."""
         for i in range(len(self.slots)):
             slot = self.slots[(self._next + i) % len(self.slots)]
             if slot.ticket is not None:
-                self.finalize(slot)
+                self.finalize(slot.ticket)
         close = getattr(self.index, "persist_close", None)
         if close is not None:  # no batch behind these: a running persistent FILTER may exit now
             close()
@@ -458,7 +488,7 @@ class ShardedSearch:
                 self._fallback(q, k, failed, kth, s_out, r_out, mask_ptr)
         else:
             self._exact(q, k, np.arange(B), s_out, r_out, mask_ptr)
-        return _Done(s_out, r_out)
+        return _Done(self, k, s_out, r_out, B)
 
     def _exact(self, q, k, which, s_out, r_out, mask_ptr):
         """Queries `which` of the batch answered by every shard's exhaustive exact top-k: one all-gather of the

@@ -538,11 +538,42 @@ class IvfIndex:
 
 class IvfShardedSearch(ShardedSearch):
     """Row-sharded IVF over the ranks (shared centroids): each rank's exact top-k of its visible
-    rows, one packed all-gather, the exact merge.  Bounds are -inf, so no fallback ever runs."""
+    rows, one packed all-gather, the exact merge.  Bounds are -inf, so no fallback ever runs.
+
+    ``k`` is the largest k a search may ask for (every rank returns its top-``k``): the candidates are exact only
+    over the probed lists, so there is no flat-scan answer for a larger k to fall back to, and submit / search
+    refuse it.  ``k`` itself is bounded by what hr_ivf_search returns per query (IVF_MAX_K) and by the merge
+    kernel's LDS (ranks * k <= MERGE_MAX_CANDIDATES)."""
+
+    IVF_MAX_K = 1024               # hr_ivf_search: 1 <= k <= 1024
+    MERGE_MAX_CANDIDATES = 8192    # k_merge sorts G * kc records in LDS (launch_merge: 16 B each, 160 KiB)
 
     def __init__(self, ivf: IvfIndex, max_batch: int, k: int, nprobe: int, group=None, depth: int = 2):
+        import torch.distributed as dist
+
+        k = int(k)
+        G = dist.get_world_size(group) if dist.is_initialized() else 1
+        limit = min(self.IVF_MAX_K, self.MERGE_MAX_CANDIDATES // G)
+        if not 1 <= k <= limit:
+            raise ValueError(f"k = {k}: an IVF sharded search over {G} rank(s) serves 1 <= k <= {limit} (hr_ivf_search "
+                             f"returns at most {self.IVF_MAX_K} rows per query, the merge holds at most "
+                             f"{self.MERGE_MAX_CANDIDATES} candidates = ranks * k)")
         super().__init__(ivf.index, 0, max_batch, kc=k, group=group, device=ivf.dev, depth=depth, overlap=False)
         self.ivf, self.nprobe = ivf, int(nprobe)
 
-    def _shard_search(self, q, k, cand, bound, mask_ptr):
+    def _check_k(self, k):
+        if int(k) > self.kc:  # (before any work: what is in flight stays in flight)
+            raise ValueError(f"k = {int(k)} above the k = {self.kc} this IVF searcher was built with (the probed lists' "
+                             "candidates have no exact answer beyond it)")
+
+    def submit(self, q, k: int, *args, **kwargs):
+        self._check_k(k)
+        return super().submit(q, k, *args, **kwargs)
+
+    def search(self, q, k: int, *args, **kwargs):
+        self._check_k(k)
+        return super().search(q, k, *args, **kwargs)
+
+    def _shard_search(self, q, k, cand, bound, mask_ptr, q_ready=None, kc=None):
+        # (q_ready: no early SAMPLE here, the queries are ready in stream order; kc: never set, k <= self.kc)
         self.ivf.search_candidates(q, self.kc, self.nprobe, cand, bound, mask_ptr=mask_ptr, stream=self._stream())

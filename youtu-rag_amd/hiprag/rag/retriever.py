@@ -124,10 +124,12 @@ class _FusedRetrieve:
         if ss is None:  # (CPU tests, multi-device handles, k beyond the pipelined path: the synchronous search)
             ran = store.search_device_sync(q, k)
             return lambda: ran
-        slot = ss.submit(q, k)
+        # (k above the searcher's kc: submit completes the cohort in flight -- its ticket keeps its answer -- and
+        # answers this one synchronously)
+        ticket = ss.submit(q, k)
 
         def finish():
-            s_out, r_out = ss.finalize(slot)
+            s_out, r_out = ss.finalize(ticket)
             return (s_out.cpu().numpy(), r_out.cpu().numpy()), tables
         return finish
 
