@@ -67,6 +67,10 @@ enum {
 #define HR_MAX_K 128           /* largest top-k (kb_file_search recall 15 x 3, rerank top-100) */
 #define HR_MAX_KC 256          /* largest per-shard candidate count kc (k = HR_MAX_K with its margin) */
 
+/* n_dev > 1: one handle over n_dev devices (dev_ids, repeats allowed), rows striped by 32-row tile.  The handle's
+ * merge takes n_dev * kc candidates per query and holds 8192 at the most, so n_dev * hr_kc_for_k_dim(HR_MAX_K, dim)
+ * <= 8192 is required -- up to 42 devices below 2048 dims, 32 from there on; more is HR_E_INVALID here (and in
+ * hr_index_load), checked with the other arguments before any device call, not a failure of the first large-k search. */
 int hr_index_create(int dim, int dtype, int metric, int n_dev, const int* dev_ids, hr_index** out);
 /* hr_index_create / hr_index_load with creation flags (single-device handles only; 0 = the plain call).
  * HR_CREATE_NO_SHADOWS: the index keeps neither the 16-bit shadow of fp32 rows nor the 8-bit shadow of a cosine

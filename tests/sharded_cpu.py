@@ -22,6 +22,26 @@ KC = 32                      # the pipelined candidate count of max_k = 16
 N_TIES = 100                 # > KC and > kc_for_k(50) = 96
 MASK_KEEP = 0.6
 
+# 3 and 8 ranks over uneven, tiny and empty shards (tests/test_dist_cpu.py on the oracle stand-ins,
+# tests/test_gpu_dist_shards.py on the kernels): NT_W rows cut at WIDE_CUTS[name], rows [DUP_W[0], DUP_W[1]) copies
+# of row 77, an odd batch (the packed record of B * kc 16-byte candidates + B 8-byte bounds is then 8 mod 16 bytes
+# long), every route of k: the pipelined kc, the scans at kc_for_k(100) and kc_for_k(128), the exhaustive pass
+NT_W, DUP_W, B_W, KS_W = 6000, (2000, 4200), 11, (10, 100, 128, 200)
+WIDE_CUTS = {
+    # a 20-row shard (< kc = 32), an empty shard, a 10-row shard; the tie block covers shards 4 and 5 whole and
+    # crosses the boundaries at 2100, 3000 and 4100
+    "w8_tiny_empty_ties": [0, 700, 720, 720, 2100, 3000, 4100, 5990, 6000],
+    "w3_ties_cross_both": [0, 2100, 4100, 6000],   # 100 copies left and right of the middle shard's 2,000
+    "w3_tiny_and_empty": [0, 25, 25, 6000],
+}
+
+
+def planted_rows(cuts):
+    """The middle row of every shard with fewer than 64 rows: a query equal to it makes that shard's candidates
+    part of the answer, so a gather that loses or misplaces a tiny shard's record cannot go unnoticed."""
+    return tuple((a + b) // 2 for a, b in zip(cuts[:-1], cuts[1:]) if 0 < b - a < 64)
+
+
 SCHEDULES = {
     "a_out_of_order": [("S", 1, 10), ("S", 2, 10), ("F", 1), ("F", 2), ("F", 2), ("F", 1)],
     "b_beyond_kc_50": [("S", 1, 10), ("S", 2, 50), ("F", 1), ("F", 2)],

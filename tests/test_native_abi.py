@@ -61,3 +61,29 @@ def test_library_loads_and_reports_errors():
         _native.NativeIndex(0, "bf16", "cosine")
     with pytest.raises(ValueError):
         _native.NativeIndex(64, "int8", "cosine")
+
+
+def test_create_refuses_device_counts_the_merge_cannot_serve():
+    """A multi-device handle merges n_dev * kc candidates per query and the merge holds 8192: with kc =
+    hr_kc_for_k_dim(HR_MAX_K, dim) = 192 (256 from 2048 dims on) that is 42 (32) devices.  hr_index_create refuses more
+    with HR_E_INVALID while it checks its arguments -- before any device call, so this runs without a GPU -- instead of
+    accepting a handle whose k = HR_MAX_K search fails.  (Accepted counts are not created here: that needs the GPU.)"""
+    import ctypes
+
+    from hiprag import _native
+
+    if not os.path.exists(_native.LIB_PATH):
+        pytest.skip("libhiprag.so not built")
+    L = _native.load_library()
+    assert _native.kc_for_k(_native.HR_MAX_K, 1024) == 192 and 42 * 192 <= 8192 < 43 * 192
+    assert _native.kc_for_k(_native.HR_MAX_K, 2048) == 256 and 32 * 256 <= 8192 < 33 * 256
+    for dim, n_dev in ((1024, 43), (64, 64), (2048, 33), (2304, 42)):
+        with pytest.raises(ValueError, match="8192"):
+            _native.NativeIndex(dim, "bf16", "cosine", devices=[0] * n_dev)
+        h = ctypes.c_void_p(1)
+        dev = (ctypes.c_int * n_dev)(*([0] * n_dev))
+        assert L.hr_index_create(dim, _native.DTYPES["bf16"], _native.METRICS["cosine"], n_dev, dev,
+                                 ctypes.byref(h)) == _native.E_INVALID
+        assert not h.value  # no handle comes back
+    with pytest.raises(ValueError, match=r"\[1, 64\]"):
+        _native.NativeIndex(64, "bf16", "cosine", devices=[0] * 65)

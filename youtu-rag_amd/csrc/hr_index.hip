@@ -75,6 +75,11 @@ extern "C" int hr_index_create_ex(int dim, int dtype, int metric, int n_dev, con
     if (dtype < F32 || dtype > F16) return set_err(HR_E_INVALID, "dtype must be HR_F32, HR_BF16 or HR_F16");
     if (metric != COSINE && metric != IP && metric != L2) return set_err(HR_E_INVALID, "unknown metric");
     if (n_dev < 1 || n_dev > 64) return set_err(HR_E_INVALID, "n_dev must be in [1, 64]");
+    // a multi-device handle's merge ranks n_dev * kc candidates per query in LDS (launch_merge: 8192 at the most) and
+    // kc reaches hr_kc_for_k_dim(HR_MAX_K, dim): a handle whose k = HR_MAX_K search could only fail is refused here
+    // (42 devices below 2048 dims, 32 from there on), before any device call
+    if (n_dev > 1 && n_dev * hr_kc_for_k_dim(HR_MAX_K, dim) > kMergeMaxCand)
+        return set_err(HR_E_INVALID, "n_dev * hr_kc_for_k_dim(HR_MAX_K, dim) must not exceed 8192 (the merge's candidates)");
     if (n_dev > 1) {
         if (!dev_ids) return set_err(HR_E_INVALID, "dev_ids required when n_dev > 1");
         return group_create(dim, dtype, metric, n_dev, dev_ids, out);

@@ -368,8 +368,9 @@ void mmr_free(hr_index* h);  // hr_mmr.hip: hr_index_destroy's part
 int launch_merge(int device, const Cand* cand, const double* bounds, int G, int B, int kc, int k, float* s_out,
                  int64_t* r_out, double* kth_out, int32_t* fail_out, hipStream_t st, int64_t cstride = 0,
                  int64_t bstride = 0);
+static constexpr int kMergeMaxCand = 8192;  // G * kc of one launch_merge: its LDS holds that many 16-byte records
 static constexpr int kFallbackCapMax = 1024;
-inline int fallback_cap(int G) { return std::max(64, std::min(kFallbackCapMax, 8192 / std::max(1, G))); }
+inline int fallback_cap(int G) { return std::max(64, std::min(kFallbackCapMax, kMergeMaxCand / std::max(1, G))); }
 
 struct FileHeader {
     char magic[8];
