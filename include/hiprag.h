@@ -213,6 +213,34 @@ int hr_index_search_mmr(hr_index* h, const float* q, int B, int k, int fetch_k, 
 int hr_index_search_mmr_device(hr_index* h, const float* q_dev, int B, int k, int fetch_k, double lambda,
                                const uint64_t* row_mask_dev, float* scores_out_dev, int64_t* rows_out_dev,
                                void* stream);
+/* Range search: every row scoring at least a threshold, with the exact count (FAISS range_search, Milvus / Qdrant
+ * score-threshold search; the reference's similarity_threshold cuts only what a guessed top_k already fetched,
+ * retriever.py:273-276).
+ * Hits: row r is a hit of query b iff it is live, the mask allows it and (float)s >= min_score[b], s the canonical
+ * fp64 score under the index's metric (cosine / ip: inner product; l2: 1 - |q - x|^2) and the cast the one
+ * hr_index_search returns -- the comparison is made on the fp32 number callers see and threshold on.  A row whose
+ * score is NaN is never a hit.  min_score[b] NaN: HR_E_INVALID; -inf makes every live, allowed row a hit; +inf is
+ * legal.
+ * counts_out[b] is the exact number of hits, also when it exceeds max_hits.  scores_out / rows_out hold the first
+ * min(count, max_hits) hits in the order every search uses (canonical fp64 score desc, row asc), scores cast to
+ * fp32, remaining slots -inf / -1: without NaN scores, hr_index_search(q_b, k = live rows) cut where its fp32 score
+ * drops below the threshold, bit for bit.
+ * Two stages: one collect pass of the corpus against a per-query floor derived from the threshold and the exactness
+ * guard's error bound, into a region of max(1024, 2 max_hits) records per query, rescored exactly, counted and
+ * ordered on the device; a query whose region overflowed goes through an all-rows pass -- canonical score of every
+ * live, allowed row, the hits compacted and only the hits sorted -- one query at a time in a workspace of 12 bytes
+ * per index row (+ 28 per hit).
+ * Limits: 0 <= max_hits <= HR_RANGE_MAX_HITS; max_hits = 0 is a count-only call (scores_out / rows_out may be
+ * NULL); any B >= 1, every dtype and metric; an empty index returns counts 0 and padding; the mask follows the
+ * rules of hr_index_search; a multi-device handle: HR_E_UNSUPPORTED.  The device form (every pointer in device
+ * memory) is ordered after the work queued on `stream` and returns with it idle. */
+#define HR_RANGE_MAX_HITS 65536
+int hr_index_search_range(hr_index* h, const float* q, int B, const float* min_score /* B */, int max_hits,
+                          const uint64_t* row_mask, float* scores_out /* B*max_hits */,
+                          int64_t* rows_out /* B*max_hits */, int64_t* counts_out /* B */);
+int hr_index_search_range_device(hr_index* h, const float* q_dev, int B, const float* min_score_dev, int max_hits,
+                                 const uint64_t* row_mask_dev, float* scores_out_dev, int64_t* rows_out_dev,
+                                 int64_t* counts_out_dev, void* stream);
 int hr_index_size(hr_index* h, int64_t* n_out, int64_t* n_live_out);
 /* Shape of a handle (e.g. one returned by hr_index_load): dim, storage dtype, metric, devices. */
 int hr_index_info(hr_index* h, int* dim_out, int* dtype_out, int* metric_out, int* n_dev_out);

@@ -81,6 +81,14 @@ int hr_index_collapse_last_ms(hr_index* h, double out[3]);
 int hr_index_set_mmr_timing(hr_index* h, int on);
 int hr_index_mmr_last_ms(hr_index* h, double out[2]);
 
+/* Diagnostics of the range search (hr_index_search_range), cumulative: queries answered by stage 1, the window scan
+ * (out[0]), queries answered by stage 2, the all-rows pass (out[1]), and window-scan launches (out[2]).  A range
+ * call moves none of hr_index_stats' counters: those count the top-k search's guard failures and exhaustive passes. */
+int hr_index_range_stats(hr_index* h, int64_t out[3]);
+/* Tiles each wave of the most recent window scan (the last chunk's collect pass) scanned, as hr_index_wave_tiles
+ * reports a FILTER's ([query group][wave], blocking; up to cap counts, the number in n_out). */
+int hr_index_range_wave_tiles(hr_index* h, uint32_t* out, int cap, int* n_out);
+
 /* Diagnostics of the pipelined search: out[0] = caller host time per submit (us), out[1] = host time
  * per batch of the busiest shard thread (us), out[2] = batches submitted. */
 int hr_index_host_us(hr_index* h, double* out);

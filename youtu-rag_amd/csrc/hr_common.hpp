@@ -163,4 +163,22 @@ __device__ inline double wave_butterfly_sum(double p) {  // canonical: p[i] + p[
     return p;
 }
 
+// Canonical fp64 score of stored row r against the processed fp32 query qv (the oracle's row_score; every exact
+// pass calls this): lane l of the wave accumulates the elements d = l (mod 64) of the padded dim in increasing d, the
+// butterfly sums the lanes; l2: euclid_score from |q|^2 (qn2), the dot and |x|^2.  Every lane of the wave must call.
+template <int DT>
+__device__ inline double canonical_score(const uint8_t* __restrict__ rows, int S, int dpad, const float* __restrict__ qv,
+                                         int metric, double qn2, int64_t r, int lane) {
+    double p = 0.0, x2 = 0.0;
+#pragma unroll 8
+    for (int d = lane; d < dpad; d += 64) {
+        const double x = (double)load_elem<DT>(rows, S, r, d);
+        p = p + x * (double)qv[d];
+        if (metric == L2) x2 = x2 + x * x;
+    }
+    p = wave_butterfly_sum(p);
+    if (metric == L2) p = euclid_score(qn2, p, wave_butterfly_sum(x2));
+    return p;
+}
+
 }  // namespace hr

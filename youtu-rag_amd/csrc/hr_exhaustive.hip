@@ -39,15 +39,7 @@ __global__ __launch_bounds__(256) void k_exact_all(const uint8_t* __restrict__ r
         }
         return;
     }
-    double p = 0.0, x2 = 0.0;
-#pragma unroll 8
-    for (int d = lane; d < dpad; d += 64) {
-        const double x = (double)hr::load_elem<DT>(rows, S, r, d);
-        p = p + x * (double)qv[d];
-        if (metric == hr::L2) x2 = x2 + x * x;
-    }
-    p = hr::wave_butterfly_sum(p);
-    if (metric == hr::L2) p = hr::euclid_score(qn2, p, hr::wave_butterfly_sum(x2));
+    const double p = hr::canonical_score<DT>(rows, S, dpad, qv, metric, qn2, r, lane);
     if (lane == 0) {
         keys[r] = hr::d2key(p);
         vals[r] = (uint32_t)r;

@@ -720,6 +720,13 @@ static int launch_scan_t(hr_index* h, Scratch& sc, int cus, const ScanArgs& a, h
         h->last_scr = &sc;
         set_dyn_tail(args, W, sc.dyn_q.as<uint32_t>());
     }
+    // range search's window scan (shard_chunk mode 2) counts its waves' tiles
+    if (MODE == SCAN_COLLECT && a.wave_tiles) {
+        const int64_t W = blocks * (TPB / 64);
+        HIP_TRY(h->rng_wtiles.ensure((size_t)ng * W * 4));
+        args.wave_tiles = h->rng_wtiles.as<uint32_t>();
+        h->rng_waves = ng * W;
+    }
     hipLaunchKernelGGL(kern, dim3((unsigned)(blocks * ng)), dim3(TPB), lds, st, args);
     HIP_TRY(hipGetLastError());
     return HR_OK;
@@ -1243,6 +1250,8 @@ struct QChunk {
 
 // One chunk of <= Bp queries on this shard.  mode 0: top-kc via SAMPLE+FILTER(groups);
 // mode 1: collect every row with approx >= floor (exact fallback).
+// mode 2 (rg): range search's window scan -- floors from rg->min_score on the stream, the collect pass appends into
+// rg->buf (rg->cap records per query), and the chunk ends there: no select, no rescore, cnt left in the workspace.
 // st_tail: stream of select + rescore (the outputs are ready in its order).  st_tail != st:
 // pipelined (mode 0 only) -- ping-pong scratch set, the scan leaves tail_cus() CUs free and the
 // tail waits for this batch's FILTER by event; st_tail == st: one stream, the synchronous set.
@@ -1253,7 +1262,7 @@ static int shard_chunk(hr_index* h, const float* q_dev, int B, int kc, int kj, c
                        const double* kth_dev_host /* mode 1: host array of kth, B */, int mode, int cap_out,
                        Cand* cand_out, double* bound_out, hipStream_t st, hipStream_t st_tail,
                        hipEvent_t q_ready = nullptr, int k8 = 0 /* the search's k: > 0 allows a shadow-8 scan */,
-                       const QChunk* qm = nullptr) {
+                       const QChunk* qm = nullptr, const RangeScan* rg = nullptr) {
     if (int rc = shadow_update(h)) return rc;
     Plan pl;
     if (int rc = make_plan(h, B, &pl)) return rc;
@@ -1478,7 +1487,11 @@ static int shard_chunk(hr_index* h, const float* q_dev, int B, int kc, int kj, c
             h->floor_host[(size_t)b] = f;
         }
     }
-    if (!fl) {
+    if (mode == 2) {
+        if (int rc = range_floors(sc.qerr.as<double>(), rg->min_score, B, Bp, max_norm, acc_gamma(h), storage_u(h),
+                                  h->metric, sc.floor_q.as<float>(), st))
+            return rc;
+    } else if (!fl) {
         HIP_TRY(hipMemcpyAsync(sc.floor_q.p, h->floor_host.data(), (size_t)Bp * 4, hipMemcpyHostToDevice, st));
     }
 
@@ -1498,6 +1511,14 @@ static int shard_chunk(hr_index* h, const float* q_dev, int B, int kc, int kj, c
     a.cnt = sc.cnt.as<uint32_t>();
     a.buf = sc.buf.as<float2>();
     a.cap = kCap;
+    if (mode == 2) {
+        a.buf = rg->buf;
+        a.cap = rg->cap;
+        // asks the collect launch for its waves' tile counts (launch_scan_t sizes the buffer)
+        HIP_TRY(h->rng_wtiles.ensure(256));
+        a.wave_tiles = h->rng_wtiles.as<uint32_t>();
+        h->rng_waves = 0;
+    }
     a.publish = 1;
     a.private_bufs = mode == 0 ? 1 : 0;
     a.wave_major = 1;
@@ -1627,6 +1648,10 @@ static int shard_chunk(hr_index* h, const float* q_dev, int B, int kc, int kj, c
                 h->ev_pending.pop_front();
             }
         }
+    }
+    if (mode == 2) {
+        if (n_vis > 0) h->n_range_scans++;
+        return HR_OK;
     }
     if (persist) {  // the tail picks the batch up once every workgroup of the instance is through it
         Persist& ps = *h->ps;
@@ -2484,6 +2509,19 @@ extern "C" int hr_index_search(hr_index* h, const float* q, int B, int k, const 
     return HR_OK;
 }
 
+// range search's window scan (hr_range.hip): Plan::Bp of a B-query call, and one chunk through shard_chunk's mode 2
+int index_plan_bp(hr_index* h, int B, int* bp_out) {
+    Plan pl;
+    if (int rc = make_plan(h, B, &pl)) return rc;
+    *bp_out = pl.Bp;
+    return HR_OK;
+}
+int index_range_chunk(hr_index* h, const float* q_dev, int bc, const uint64_t* mask_dev, const RangeScan* rs,
+                      hipStream_t st) {
+    if (int rc = persist_close(h)) return rc;  // a running persistent FILTER leaves the CUs to this scan
+    return shard_chunk(h, q_dev, bc, 1, 0, mask_dev, 0, nullptr, 2, 1, nullptr, nullptr, st, st, nullptr, 0, nullptr, rs);
+}
+
 // one shard's exact candidates (group handles, hr_group.hip)
 int index_shard_search(hr_index* h, const float* q_dev, int B, int kc, int kj, const uint64_t* mask_dev, Cand* cand_out,
                        double* bound_out, hipStream_t st) {
@@ -2861,6 +2899,7 @@ extern "C" void hr_index_destroy(hr_index* h) {
     if (h->xnorm) (void)hipFree(h->xnorm);
     if (h->norm_bits) (void)hipFree(h->norm_bits);
     collapse_free(h);
+    range_free(h);
     mmr_free(h);
     (void)hipDeviceSynchronize();  // pipelined batches may still run on caller streams
     for (auto& g : h->sync_graphs)

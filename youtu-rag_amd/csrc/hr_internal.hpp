@@ -303,6 +303,14 @@ struct hr_index {
     bool mmr_timing = false;          // hr_index_set_mmr_timing: HIP events around the two stages of every call
     hipEvent_t mmr_ev[3] = {nullptr, nullptr, nullptr};
     double mmr_ms[2] = {0.0, 0.0};    // probe search, selection kernel of the most recent timed call
+    // ---- range search (hr_range.hip): every buffer allocated by the first call that needs it.  rng_arena: per query
+    // of a chunk one region of cap float2 scan records and cap score keys; rng_keys: stage 2's score keys + rows of
+    // ONE query (12 n bytes) or a large region's row-ordered copy; rng_sort: the hits of one query being sorted
+    DevBuf rng_q, rng_t, rng_mask, rng_out, rng_arena, rng_flag, rng_keys, rng_sort, rng_tmp;
+    int64_t n_range_window = 0, n_range_all = 0;  // queries answered by stage 1 (window scan) / stage 2 (all rows)
+    int64_t n_range_scans = 0;                    // window-scan launches (one per chunk of queries)
+    DevBuf rng_wtiles;                            // diagnostics: tiles each wave of the most recent window scan scanned
+    int64_t rng_waves = 0;                        // ... and how many waves that launch had (all query groups)
 };
 
 // an internal stream of h: on h's CU mask when one is set (priority is then not available), else high priority or
@@ -364,6 +372,21 @@ int index_search_locked(hr_index* h, const float* q_dev, int B, int k, const uin
 int index_prep_exact(hr_index* h, const float* q_dev, int B, hipStream_t st, const float** q32_out,
                      std::vector<double>* qerr_out);
 void collapse_free(hr_index* h);
+// range search (hr_range.hip) reaches the collect scan through shard_chunk's mode 2: query prep, floors from the
+// caller's thresholds (range_floors, on the stream: no host wait), one SCAN_COLLECT pass appending into the caller's
+// regions, and nothing after it -- the counts are left in the synchronous workspace's cnt (h->scr[kSyncSet]), its q32
+// / qerr hold the chunk's processed queries.  index_range_chunk: one chunk of bc <= index_plan_bp(h, B) queries.
+struct RangeScan {
+    const float* min_score;  // device, one per query of the chunk
+    float2* buf;             // [Bp][cap] records {approximate score, row bits}
+    int cap;
+};
+int index_plan_bp(hr_index* h, int B, int* bp_out);
+int index_range_chunk(hr_index* h, const float* q_dev, int bc, const uint64_t* mask_dev, const RangeScan* rs,
+                      hipStream_t st);
+int range_floors(const double* qerr, const float* min_score, int B, int Bp, double max_norm, double gamma, double u_x,
+                 int metric, float* floor_q, hipStream_t st);
+void range_free(hr_index* h);  // hr_index_destroy's part
 void mmr_free(hr_index* h);  // hr_mmr.hip: hr_index_destroy's part
 int launch_merge(int device, const Cand* cand, const double* bounds, int G, int B, int kc, int k, float* s_out,
                  int64_t* r_out, double* kth_out, int32_t* fail_out, hipStream_t st, int64_t cstride = 0,

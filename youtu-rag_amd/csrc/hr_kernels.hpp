@@ -1452,18 +1452,7 @@ __global__ __launch_bounds__(256) void k_rescore(const uint8_t* __restrict__ row
     }
     const int64_t r = (int64_t)sel_rows[q * kc + c];
     const float* qv = q32 + (int64_t)q * dpad;
-    double p = 0.0, x2 = 0.0;
-#pragma unroll 8
-    for (int d = lane; d < dpad; d += 64) {
-        const double x = (double)load_elem<DT>(rows, S, r, d);
-        p = p + x * (double)qv[d];
-        if (metric == L2) x2 = x2 + x * x;
-    }
-    p = wave_butterfly_sum(p);
-    if (metric == L2) {
-        x2 = wave_butterfly_sum(x2);
-        p = euclid_score(qn2, p, x2);
-    }
+    const double p = canonical_score<DT>(rows, S, dpad, qv, metric, qn2, r, lane);
     if (lane == 0) out[wid] = Cand{p, stripe_row(r, sG, ss) + row_offset};
 }
 

@@ -20,6 +20,7 @@ DTYPES = {"f32": 0, "float32": 0, "fp32": 0, "bf16": 1, "bfloat16": 1, "f16": 2,
 METRICS = {"cosine": 0, "ip": 1, "dot": 1, "euclidean": 2, "l2": 2}
 HR_MAX_K = 128   # include/hiprag.h
 HR_MAX_KC = 256
+HR_RANGE_MAX_HITS = 65536  # largest max_hits of search_range
 HR_CREATE_NO_SHADOWS = 1
 HR_LEX_TERM_BITS = 22    # term id = crc32(token) % 2**22
 HR_LEX_MAX_QTERMS = 64
@@ -61,6 +62,8 @@ EXPORTS = [
     "hr_index_search_masks", "hr_index_search_masks_device", "hr_index_qmask_launches",
     "hr_index_set_qmask_timing", "hr_index_qmask_last_ms",
     "hr_index_search_mmr", "hr_index_search_mmr_device", "hr_index_set_mmr_timing", "hr_index_mmr_last_ms",
+    "hr_index_search_range", "hr_index_search_range_device", "hr_index_range_stats",
+    "hr_index_range_wave_tiles",
 ]
 
 _lib = None
@@ -218,6 +221,10 @@ def load_library(path: str | None = None):
             "hr_index_search_mmr_device": [vp, vp, i32, i32, i32, ctypes.c_double, vp, vp, vp, vp],
             "hr_index_set_mmr_timing": [vp, i32],
             "hr_index_mmr_last_ms": [vp, vp],
+            "hr_index_search_range": [vp, vp, i32, vp, i32, vp, vp, vp, vp],
+            "hr_index_search_range_device": [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp],
+            "hr_index_range_stats": [vp, vp],
+            "hr_index_range_wave_tiles": [vp, vp, i32, vp],
         }
         for name, args in sig.items():
             if p != (path or LIB_PATH) and not hasattr(L, name):
@@ -543,6 +550,54 @@ class NativeIndex:
         out = (ctypes.c_double * 2)()
         _check(self.lib.hr_index_mmr_last_ms(self._h, out))
         return {"probe_ms": out[0], "select_ms": out[1]}
+
+    # -- range search (hr_range.hip): every row scoring at least a threshold, with the exact count
+    def search_range(self, q: np.ndarray, min_score, max_hits: int = 1024, mask: np.ndarray | None = None):
+        """Every live, allowed row whose fp32 score is >= ``min_score`` (a scalar or one value per query), exactly
+        (hr_index_search_range): ``(scores, rows, counts)`` -- the first min(count, max_hits) hits of every query in
+        search()'s order, -inf / -1 after them, and the exact number of hits, also beyond ``max_hits``.
+        ``max_hits = 0`` only counts: ``(None, None, counts)``."""
+        q = np.ascontiguousarray(q, np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.shape[1] != self.dim:
+            raise ValueError(f"query dim {q.shape[1]} != index dim {self.dim}")
+        B = q.shape[0]
+        t = np.ascontiguousarray(np.broadcast_to(np.asarray(min_score, np.float32).reshape(-1), (B,)))
+        max_hits = int(max_hits)
+        if max_hits < 0 or max_hits > HR_RANGE_MAX_HITS:  # (before the output arrays are sized by it)
+            raise ValueError(f"max_hits must be in [0, {HR_RANGE_MAX_HITS}]")
+        s = np.empty((B, max_hits), np.float32) if max_hits else None
+        r = np.empty((B, max_hits), np.int64) if max_hits else None
+        c = np.zeros(B, np.int64)
+        m = self._mask_words(mask)
+        _check(self.lib.hr_index_search_range(self._h, _ptr(q), B, _ptr(t), max_hits, _ptr(m), _ptr(s), _ptr(r),
+                                              _ptr(c)))
+        return s, r, c
+
+    def search_range_device(self, q_ptr: int, B: int, min_score_ptr: int, max_hits: int, scores_ptr: int,
+                            rows_ptr: int, counts_ptr: int, mask_ptr: int = 0, stream: int = 0) -> None:
+        """search_range() with every array in device memory (B fp32 thresholds, B int64 counts); ordered after the
+        work queued on ``stream``, which is idle on return."""
+        _check(self.lib.hr_index_search_range_device(self._h, ctypes.c_void_p(q_ptr), int(B),
+                                                     ctypes.c_void_p(min_score_ptr), int(max_hits),
+                                                     ctypes.c_void_p(mask_ptr or None),
+                                                     ctypes.c_void_p(scores_ptr or None),
+                                                     ctypes.c_void_p(rows_ptr or None), ctypes.c_void_p(counts_ptr),
+                                                     ctypes.c_void_p(stream or None)))
+
+    def range_stats(self) -> dict:
+        """Cumulative range queries answered by the window scan / by the all-rows pass, and window-scan launches."""
+        out = (ctypes.c_int64 * 3)()
+        _check(self.lib.hr_index_range_stats(self._h, out))
+        return {"window": int(out[0]), "all_rows": int(out[1]), "scans": int(out[2])}
+
+    def range_wave_tiles(self, cap: int = 1 << 16) -> np.ndarray:
+        """Tiles each wave of the most recent window scan of search_range scanned (hr_index_range_wave_tiles)."""
+        out = np.zeros(cap, np.uint32)
+        n = ctypes.c_int(0)
+        _check(self.lib.hr_index_range_wave_tiles(self._h, _ptr(out), int(cap), ctypes.byref(n)))
+        return out[: n.value].copy()
 
     def search_device(self, q_ptr: int, B: int, k: int, scores_ptr: int, rows_ptr: int, mask_ptr: int = 0,
                       stream: int = 0) -> None:

@@ -213,6 +213,13 @@ class IvfStoreIndex:
     def search_mmr(self, q: np.ndarray, k: int, lam: float, mask: np.ndarray | None = None, fetch_k: int = 0):
         return self.exact.search_mmr(q, k, lam, mask, fetch_k)
 
+    # a range answer is exact by definition (every row at or above the threshold): the exact index answers
+    def search_range(self, q: np.ndarray, min_score, max_hits: int = 1024, mask: np.ndarray | None = None):
+        return self.exact.search_range(q, min_score, max_hits, mask)
+
+    def range_stats(self) -> dict:
+        return self.exact.range_stats()
+
     # ---------------------------------------------------------------- persistence
     def save(self, path: str) -> None:
         """The exact index to ``path`` as ever, and ``path + ".ivf.npz"``: centroids, nlist, the seed, the list of

@@ -310,6 +310,22 @@ class VectorRetriever(BaseRetriever):
                                               filters=kwargs.get("filters"), **extra)
         return await self._finish(query, self._to_results(hits, threshold), top_k)
 
+    async def retrieve_above(self, query: str, threshold: float | None = None, limit: int = 1024,
+                             filters: dict | None = None) -> list[RetrievalResult]:
+        """Every chunk scoring at least ``threshold``, best first, at most ``limit`` of them: the store's range
+        search, so nothing relevant hides below a guessed top_k.  ``None`` means ``config.similarity_threshold`` and
+        the value is used as given -- here 0.0 is a threshold like any other, unlike retrieve(), where <= 0 disables
+        the cut.  Ranks are 1-based; the optional reranker and the final cut apply as in retrieve()."""
+        search_range = getattr(self.vector_store, "search_range", None)
+        if search_range is None:
+            raise NotImplementedError(f"{type(self.vector_store).__name__} has no range search")
+        t = self.config.similarity_threshold if threshold is None else threshold
+        qv = await self.embedder.embed_query(query)
+        found = await search_range(query_embedding=qv, min_score=float(t), max_hits=int(limit), filters=filters)
+        results = [RetrievalResult(chunk=chunk, score=score, rank=pos + 1)
+                   for pos, (chunk, score) in enumerate(found.hits)]
+        return await self._finish(query, results, int(limit))
+
     async def batch_retrieve(self, queries: list[str], top_k: int | None = None, **kwargs
                              ) -> list[list[RetrievalResult]]:
         return [await self.retrieve(query=q, top_k=top_k, **kwargs) for q in queries]

@@ -59,6 +59,12 @@ from the exact top-``fetch_k`` (hr_index_search_mmr).  The hits co
 plain-search scores, so the scores are not monotone.  Concurrent MMR queries of one (lambda, fetch_k, filter) share a
 launch whatever their ``top_k``.  Not combined with ``collapse``.
 
+Range search (``search_range_batch(qs, min_score, max_hits)`` / ``count_above_batch`` / ``await search_range``; single
+device): every chunk scoring at least ``min_score`` -- one threshold or one per query -- and the exact number of them,
+not the best k of a guessed ``top_k`` (hr_index_search_range).  Each query gets a ``RangeHits(hits,
+total)``: the first ``max_hits`` hits, best first, and the count whatever ``max_hits`` is (``truncated``: the list was
+cut).  Range calls do not go through the micro-batcher; the single-query form runs in a worker thread.
+
 ``index_type: "IVF_FLAT"`` (any letter case; single device, cosine / dot): the index is an ``IvfStoreIndex``
 (ivf_store.py) -- the same exact index plus an IVF replica that answers searches once ``ivf_train_rows`` live rows
 are stored (``index_params``: nlist, nprobe, ivf_train_rows = 64 nlist, ivf_seed).  It comes in through the
@@ -75,7 +81,7 @@ import os
 import threading
 from array import array
 from collections import deque
-from typing import Any
+from typing import Any, NamedTuple
 
 import numpy as np
 
@@ -136,6 +142,18 @@ def _assemble_results_py(C, R, rec_l, meta_l, score_l, per_q, embs, ks, ths, unt
 logger = logging.getLogger(__name__)
 
 _METRIC = {"cosine": "cosine", "dot": "ip", "euclidean": "l2"}
+
+
+class RangeHits(NamedTuple):
+    """One query's answer to a range search: the first ``max_hits`` hits, best first, and the exact number of rows
+    at or above the threshold."""
+    hits: list
+    total: int
+
+    @property
+    def truncated(self) -> bool:
+        """More rows reached the threshold than ``hits`` holds."""
+        return self.total > len(self.hits)
 
 
 class _ObjColumn:
@@ -1266,6 +1284,93 @@ class HipVectorStore(BaseVectorStore):
         if int(top_k) > _native.HR_MAX_K:  # checked before queueing: a bad query fails alone
             raise ValueError(f"a collapsed search returns at most {_native.HR_MAX_K} groups (top_k = {top_k})")
         return await self._batcher.submit(q, top_k, filters, collapse=True)
+
+    # -- range search (hr_index_search_range): every chunk scoring at least min_score, and how many
+    def _prep_range(self, query_embeddings, min_score, max_hits: int, filters):
+        """(q, thresholds, max_hits, filters) of a range search, every limit checked: a bad request fails here,
+        before any native call."""
+        q = np.asarray(query_embeddings, dtype=np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        dim = self.dim
+        if dim is not None and q.shape[1] != dim:
+            raise ValueError(f"query dim {q.shape[1]} != collection dim {dim}")
+        max_hits = int(max_hits)
+        if max_hits < 0 or max_hits > _native.HR_RANGE_MAX_HITS:
+            raise ValueError(f"max_hits must be in [0, {_native.HR_RANGE_MAX_HITS}] (got {max_hits})")
+        t = np.asarray(min_score, np.float32).reshape(-1)
+        if len(t) not in (1, q.shape[0]):
+            raise ValueError(f"{len(t)} thresholds for {q.shape[0]} queries")
+        t = np.ascontiguousarray(np.broadcast_to(t, (q.shape[0],)))
+        if np.isnan(t).any():
+            raise ValueError("min_score must not be NaN")
+        if isinstance(filters, (list, tuple)):  # one where-clause (or None) per query
+            filters = list(filters)
+            if len(filters) != q.shape[0]:
+                raise ValueError(f"{len(filters)} filters for {q.shape[0]} queries")
+            if len({_filter_key(f) for f in filters}) == 1:
+                filters = filters[0] or None
+        if len(getattr(self._index, "devices", (0,))) > 1:
+            raise ValueError("a range search needs a single-device store")
+        return q, t, max_hits, filters
+
+    def _run_range(self, prep):
+        """The native range search under the store lock, as _run_search: ((scores, rows) or None, counts, tables).  A
+        per-query filter list runs one call per distinct where-clause, scattered back in query order."""
+        q, t, max_hits, filters = prep
+        B = q.shape[0]
+        with self._lock:  # ordered against mutations
+            tables = (self._records, self._metas, self._epoch)
+            idx = self._index
+            counts = np.zeros(B, np.int64)
+            if idx is None or self.count_sync() == 0:
+                return None, counts, tables
+            if len(getattr(idx, "devices", (0,))) > 1:
+                raise ValueError("a range search needs a single-device store")
+            if not hasattr(idx, "search_range"):
+                raise NotImplementedError(f"{type(idx).__name__} has no range search")
+            if not isinstance(filters, list):
+                s, r, counts = idx.search_range(q, t, max_hits, self.filter_bitmap(filters))
+                return (None if s is None else (s, r)), np.asarray(counts, np.int64), tables
+            clauses, clause_of, bitmaps = self._distinct_filters(filters)
+            scores = np.full((B, max_hits), -np.inf, np.float32)
+            rows_out = np.full((B, max_hits), -1, np.int64)
+            for c in range(len(clauses)):
+                sel = np.nonzero(clause_of == c)[0]
+                s, r, n = idx.search_range(q[sel], t[sel], max_hits, bitmaps[c])
+                self.grouped_launches += 1
+                counts[sel] = n
+                if max_hits:
+                    scores[sel], rows_out[sel] = s, r
+            return ((scores, rows_out) if max_hits else None), counts, tables
+
+    def search_range_batch(self, query_embeddings, min_score, max_hits: int = 1024, filters=None) -> list[RangeHits]:
+        """Every stored chunk whose score is at least ``min_score`` (a scalar or one value per query), exactly: per
+        query a RangeHits of the first ``max_hits`` hits, best first, and the exact total -- ``truncated`` tells
+        whether the list was cut.  ``filters``: one where-clause, or a list with one (or None) per query."""
+        prep = self._prep_range(query_embeddings, min_score, max_hits, filters)
+        raw, counts, tables = self._run_range(prep)
+        B = len(prep[0])
+        if raw is None:
+            return [RangeHits([], int(counts[b])) for b in range(B)]
+        lists = self._assemble(prep, (raw, tables))
+        return [RangeHits(lists[b], int(counts[b])) for b in range(B)]
+
+    def count_above_batch(self, query_embeddings, min_score, filters=None) -> list[int]:
+        """How many stored chunks score at least ``min_score``, per query: the count-only range search."""
+        prep = self._prep_range(query_embeddings, min_score, 0, filters)
+        return [int(c) for c in self._run_range(prep)[1]]
+
+    async def search_range(self, query_embedding: list[float], min_score: float, max_hits: int = 1024,
+                           filters: dict[str, Any] | None = None) -> RangeHits:
+        """One query's range search, off the event loop (a range call is a corpus pass of its own, not a
+        micro-batched top-k)."""
+        q = np.asarray(query_embedding, dtype=np.float32).reshape(1, -1)
+        prep = self._prep_range(q, min_score, max_hits, filters)  # checked here: a bad request fails alone
+        raw, counts, tables = await asyncio.to_thread(self._run_range, prep)
+        if raw is None:
+            return RangeHits([], int(counts[0]))
+        return RangeHits(self._assemble(prep, (raw, tables))[0], int(counts[0]))
 
     def get_by_id_sync(self, chunk_id: str) -> Chunk | None:
         with self._lock:
