@@ -138,8 +138,10 @@ __device__ inline float gen_elem(uint64_t seed, int64_t row, int dim, int d) {
 // Guard bound on |approx - exact| of the scan score of query q (DESIGN.md "Exactness guard"):
 // inner product E = max|x| (|q - q̂| + (gamma + u_x) |q̂|); euclidean (scan score 2 q̂.x - |x|^2 in
 // fp32) adds the doubled dot error, the fp32 rounding of |x|^2 and of the fused multiply-add.
+// qe[3] (0 unless the query was prepared for a shadow-8 scan): what the scan's bias fold adds, at the largest row
+// scale (k_prep_q).
 __device__ __host__ inline double guard_e(const double* qe, double max_norm, double gamma, double u_x, int metric) {
-    const double E = max_norm * (qe[0] * (1.0 + 1e-6) + (gamma + u_x) * qe[1]) + 1e-9;
+    const double E = (max_norm * (qe[0] * (1.0 + 1e-6) + (gamma + u_x) * qe[1]) + 1e-9) + qe[3];
     if (metric != L2) return E;
     return 2.0 * E + 0x1p-22 * (max_norm * max_norm + 2.0 * max_norm * qe[1]) + 1e-9;
 }

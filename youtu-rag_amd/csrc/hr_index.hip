@@ -108,8 +108,8 @@ extern "C" int hr_index_create_ex(int dim, int dtype, int metric, int n_dev, con
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipMalloc(&h->norm_bits, sizeof(unsigned long long));
     if (e == hipSuccess) e = hipMemset(h->norm_bits, 0, sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMalloc(&h->err8_bits, sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMemset(h->err8_bits, 0, sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMalloc(&h->err8_bits, 2 * sizeof(unsigned long long));  // [1]: the largest row scale's bits
+    if (e == hipSuccess) e = hipMemset(h->err8_bits, 0, 2 * sizeof(unsigned long long));
     hipDeviceProp_t prop;
     if (e == hipSuccess) e = hipGetDeviceProperties(&prop, dev);
     if (e != hipSuccess) {
@@ -670,10 +670,11 @@ static int region_slots(const hr_index* h, int64_t W, int64_t W_dev, int64_t n_u
     return kCapW * (int)std::max<int64_t>(1, scale);
 }
 
-template <int MT, int DT, int QB, int P, int MODE, bool NT, int TPB = kScanThreads, bool QM = false, bool THL = false>
+template <int MT, int DT, int QB, int P, int MODE, bool NT, int TPB = kScanThreads, bool QM = false, bool THL = false,
+          bool BF = false>
 static int launch_scan_t(hr_index* h, Scratch& sc, int cus, const ScanArgs& a, hipStream_t st, int lds) {
     const int ng = std::max(1, a.ng);
-    auto kern = scan_kernel<MT, DT, QB, P, MODE, NT, TPB, QM, THL>();
+    auto kern = scan_kernel<MT, DT, QB, P, MODE, NT, TPB, QM, THL, BF>();
     static std::mutex attr_mu;
     static int attr_lds[64] = {};     // per device: largest dynamic LDS already allowed
     static int occ[64][4] = {};       // per device: blocks/CU for lds buckets (0 = unknown), per instantiation
@@ -850,6 +851,13 @@ static int launch_scan(hr_index* h, Scratch& sc, int cus, const Plan& pl, const 
     });
 }
 
+// the shadow-8 scans' bias fold (scan_body: BF): its row of QB*32 floats fits in LDS behind the query tile and the
+// threshold row -- everywhere but where the tile fills the 160 KiB (D = 1280 at QB = 2); k_debug_approx follows the scan
+// (and k_prep_q sums the fold's terms over the 64 kPrepJ elements it holds in registers: every plan's dpad, make_plan)
+static bool fold8_fits(const hr_index* h, int QB) {
+    return scan_lds_bytes(h, QB) + 2 * QB * 32 * 4 <= 160 * 1024 && h->dpad <= 64 * kPrepJ;
+}
+
 // the shadow-8 SAMPLE / 64-query FILTER (XFrag<F16, I8S>): f16 queries whatever the stored dtype, a ring of P8
 // 16-byte loads (each a pair of k-steps), P8 the deepest of 16 / 8 / 4 / 2 dividing S / 2.  One query group only.
 template <int MODE>
@@ -865,15 +873,26 @@ static int launch_scan8(hr_index* h, Scratch& sc, int cus, const Plan& pl, const
     // at QB = 2 fills the 160 KiB) and the plan has at most the five row parts a slice is loaded for
     ScanArgs a = a_;
     a.th_off = 0;
-    if (MODE == SCAN_FILTER && kRefreshLds && a.use_groups && a.np <= 5 && lds + pl.QB * 32 * 4 <= 160 * 1024) {
+    // The bias fold's row of -C_q (ScanArgs::qb_off) goes behind both; where it does not fit (fold8_fits: D = 1280 at
+    // QB = 2) neither does the threshold row, and the scan is the subtracting one.
+    const bool fold = MODE == SCAN_FILTER && fold8_fits(h, pl.QB) && a.qbias;  // (the SAMPLE keeps the subtract)
+    if (MODE == SCAN_FILTER && kRefreshLds && a.use_groups && a.np <= 5 && fold) {
         a.th_off = lds;
+        lds += pl.QB * 32 * 4;
+    }
+    a.qb_off = 0;
+    if (fold) {
+        a.qb_off = lds;
         lds += pl.QB * 32 * 4;
     }
 #define HR_SCAN8_CASE(QBv, Pv)                                                                                      \
     if (pl.QB == QBv && P8 == Pv) {                                                                                 \
         if constexpr (MODE == SCAN_FILTER)                                                                          \
             if (a.th_off)                                                                                           \
-                return launch_scan_t<F16, I8S, QBv, Pv, MODE, NT, kScanThreads, false, true>(h, sc, cus, a, st, lds); \
+                return launch_scan_t<F16, I8S, QBv, Pv, MODE, NT, kScanThreads, false, true, true>(h, sc, cus, a, st, lds); \
+        if constexpr (MODE == SCAN_FILTER)                                                                          \
+            if (a.qb_off)                                                                                           \
+                return launch_scan_t<F16, I8S, QBv, Pv, MODE, NT, kScanThreads, false, false, true>(h, sc, cus, a, st, lds); \
         return launch_scan_t<F16, I8S, QBv, Pv, MODE, NT>(h, sc, cus, a, st, lds);                                  \
     }
     HR_SCAN8_CASE(2, 16) HR_SCAN8_CASE(1, 16) HR_SCAN8_CASE(2, 8) HR_SCAN8_CASE(1, 8) HR_SCAN8_CASE(2, 4)
@@ -1129,6 +1148,7 @@ __global__ __launch_bounds__(256) void k_shadow8(const uint8_t* __restrict__ row
         // (rounded up: the guard takes this as an upper bound)
         const double e = __builtin_sqrt(e2) * (1.0 + 0x1p-40);
         atomicMax(err_bits, (unsigned long long)__builtin_bit_cast(uint64_t, e));
+        atomicMax(err_bits + 1, (unsigned long long)__builtin_bit_cast(uint32_t, scale));  // (the bias fold's guard term)
     }
 }
 
@@ -1150,12 +1170,16 @@ static int shadow8_update(hr_index* h, bool force = false) {
             return HR_OK;
         });
         if (rc) return rc;
-        unsigned long long bits = 0;
-        HIP_TRY(hipMemcpyAsync(&bits, h->err8_bits, sizeof(bits), hipMemcpyDeviceToHost, h->stream));
+        unsigned long long bits[2] = {0, 0};
+        HIP_TRY(hipMemcpyAsync(bits, h->err8_bits, sizeof(bits), hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(hipStreamSynchronize(h->stream));
         double v;
-        std::memcpy(&v, &bits, 8);
+        std::memcpy(&v, &bits[0], 8);
         h->err8 = std::max(h->err8, v);
+        float sm;
+        const uint32_t sbits = (uint32_t)bits[1];
+        std::memcpy(&sm, &sbits, 4);
+        h->scale8_max = std::max(h->scale8_max, sm);
     }
     h->shadow8_lo = INT64_MAX;
     return HR_OK;
@@ -1438,6 +1462,9 @@ static int shard_chunk(hr_index* h, const float* q_dev, int B, int kc, int kj, c
     HIP_TRY(sc.q32.ensure((size_t)Bp * h->dpad * 4));
     HIP_TRY(sc.qfrag.ensure((size_t)pl.NG * h->S * pl.QB * 1024));
     HIP_TRY(sc.qerr.ensure((size_t)Bp * 4 * 8));
+    if (use8) {
+        HIP_TRY(sc.qbias.ensure((size_t)Bp * 4));
+    }
     // row parts for the group-max bound: 32 groups bound the 32nd best, so kc > 32 needs ceil(kc/32) parts
     const int np = mode == 0 ? (kc + 31) / 32 : 1;
     HIP_TRY(sc.mkeys.ensure((size_t)np * Bp * 32 * 4));
@@ -1459,7 +1486,8 @@ static int shard_chunk(hr_index* h, const float* q_dev, int B, int kc, int kj, c
     else
         hipLaunchKernelGGL((k_prep_q<F16>), dim3((Bp + 3) / 4), dim3(256), 0, sp, q_dev, B, Bp, h->dim, h->dpad, h->S,
                            pl.QB, h->metric, sc.q32.as<float>(), sc.qfrag.as<uint16_t>(), sc.qerr.as<double>(),
-                           sc.mkeys.as<uint32_t>(), np, sc.cnt.as<uint32_t>(), fl, sc.dyn_q.as<uint32_t>());
+                           sc.mkeys.as<uint32_t>(), np, sc.cnt.as<uint32_t>(), fl, sc.dyn_q.as<uint32_t>(),
+                           use8 && fold8_fits(h, pl.QB) ? sc.qbias.as<float>() : nullptr, (double)h->scale8_max);
     HIP_TRY(hipGetLastError());
 
     // floors: padded queries never collect; mode 1 uses kth - E (computed on the host from qerr)
@@ -1498,6 +1526,7 @@ static int shard_chunk(hr_index* h, const float* q_dev, int B, int kc, int kj, c
     ScanArgs a{};
     a.rows = use8 ? h->rows8 : scan_rows(h);
     a.rscale = use8 ? h->scale8 : nullptr;
+    a.qbias = use8 && fold8_fits(h, pl.QB) ? sc.qbias.as<float>() : nullptr;  // (else the subtracting FILTER, no guard term)
     a.xnorm = h->metric == L2 ? h->xnorm : nullptr;
     a.live = h->live;
     a.mask = qm ? sc.qallow.as<uint32_t>() : (const uint32_t*)mask_dev;  // (QM scans: the allow table)
@@ -2040,7 +2069,7 @@ static int sync_graph_search(hr_index* h, const float* q, int B, int k, float* s
     auto current = [&](const hr_index::SyncGraph& g) {
         return g.exec && g.n == h->n && g.rows == h->rows && g.live == h->live && g.xnorm == h->xnorm &&
                g.max_norm2 == h->max_norm2 && g.pin == h->pin && g.buf_gen == g_buf_gen.load() &&
-               g.rows8 == h->rows8 && g.err8 == h->err8;  // (the shadow-8 guard term is a captured argument)
+               g.rows8 == h->rows8 && g.err8 == h->err8 && g.scale8_max == h->scale8_max;  // (the shadow-8 guard term is a captured argument)
     };
     if (!current(*e)) {
         if (e->exec) {  // stale: recapture right away after a buffer moved; after the rows changed
@@ -2104,6 +2133,7 @@ static int sync_graph_search(hr_index* h, const float* q, int B, int k, float* s
         e->max_norm2 = h->max_norm2;
         e->rows8 = h->rows8;
         e->err8 = h->err8;
+        e->scale8_max = h->scale8_max;
         e->pin = h->pin;
         e->buf_gen = gen0;
     }
@@ -2684,8 +2714,12 @@ static int debug_approx_impl(hr_index* h, const float* q, int B, float* approx_o
     const int64_t n_tiles = (h->n + 31) / 32;
     HIP_TRY(h->q_in.ensure((size_t)B * h->dim * 4));
     HIP_TRY(sc.q32.ensure((size_t)Bp * h->dpad * 4));
-    HIP_TRY(sc.qfrag.ensure((size_t)h->S * pl.QB * 1024));
+    // (every query group's fragments: k_prep_q writes all Bp queries, the kernel below reads the first group's)
+    HIP_TRY(sc.qfrag.ensure((size_t)pl.NG * h->S * pl.QB * 1024));
     HIP_TRY(sc.qerr.ensure((size_t)Bp * 4 * 8));
+    if (s8) {
+        HIP_TRY(sc.qbias.ensure((size_t)Bp * 4));
+    }
     HIP_TRY(h->stage.ensure((size_t)Bp * n_tiles * 32 * 4 + 16));
     HIP_TRY(hipMemcpyAsync(h->q_in.p, q, (size_t)B * h->dim * 4, hipMemcpyHostToDevice, st));
     const int MT = s8 ? F16 : mfma_type(h);
@@ -2696,14 +2730,17 @@ static int debug_approx_impl(hr_index* h, const float* q, int B, float* approx_o
     else
         hipLaunchKernelGGL((k_prep_q<F16>), dim3((Bp + 3) / 4), dim3(256), 0, st, h->q_in.as<float>(), B, Bp, h->dim,
                            h->dpad, h->S, pl.QB, h->metric, sc.q32.as<float>(), sc.qfrag.as<uint16_t>(), sc.qerr.as<double>(),
-                           nullptr, 1, nullptr, nullptr, nullptr);
+                           nullptr, 1, nullptr, nullptr, nullptr,
+                           s8 && fold8_fits(h, pl.QB) ? sc.qbias.as<float>() : nullptr,
+                           (double)h->scale8_max);
     HIP_TRY(hipGetLastError());
     const int lds = scan_lds_bytes(h, pl.QB);
     int rc = s8 ? [&]() -> int {
         auto kern = pl.QB == 1 ? k_debug_approx<F16, I8S, 1> : k_debug_approx<F16, I8S, 2>;
         HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         hipLaunchKernelGGL(kern, dim3((unsigned)((n_tiles + 3) / 4)), dim3(256), lds, st, h->rows8,
-                           sc.qfrag.as<uint16_t>(), h->S, n_tiles, nullptr, h->stage.as<float>(), h->scale8);
+                           sc.qfrag.as<uint16_t>(), h->S, n_tiles, nullptr, h->stage.as<float>(), h->scale8,
+                           s8 && fold8_fits(h, pl.QB) ? sc.qbias.as<float>() : (const float*)nullptr);
         HIP_TRY(hipGetLastError());
         return HR_OK;
     }() : dispatch_dt(h->dtype, [&](auto dt) -> int {
@@ -2718,7 +2755,7 @@ static int debug_approx_impl(hr_index* h, const float* q, int B, float* approx_o
         HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         hipLaunchKernelGGL(kern, dim3((unsigned)((n_tiles + 3) / 4)), dim3(256), lds, st, h->rows,
                            sc.qfrag.as<uint16_t>(), h->S, n_tiles, h->metric == L2 ? h->xnorm : nullptr,
-                           h->stage.as<float>(), (const float*)nullptr);
+                           h->stage.as<float>(), (const float*)nullptr, (const float*)nullptr);
         HIP_TRY(hipGetLastError());
         return HR_OK;
     });

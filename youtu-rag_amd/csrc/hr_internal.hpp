@@ -125,7 +125,8 @@ struct Scratch {
         wtiles,      // diagnostics: tiles each wave of the most recent FILTER launch scanned (ScanArgs::wave_tiles)
         cand8,       // shadow-8 scan: the exact candidates of its deeper kc, before the trim to the caller's kc
         qunion,      // per-query masks: OR of the chunk's bitmaps, one word per tile (the tile list's mask)
-        qallow;      // per-query masks: lane-order allow words, [tile][64] (the QM scans' ScanArgs::mask)
+        qallow,      // per-query masks: lane-order allow words, [tile][64] (the QM scans' ScanArgs::mask)
+        qbias;       // shadow-8 scan: -C_q per padded query, the accumulators' start value (k_prep_q, ScanArgs::qbias)
     int64_t last_W = 0, last_Bp = 0;  // waves (per query group) and queries per group of the most recent FILTER
     int last_ng = 1;                  // query groups of that launch
     int last_capw = kCapW;            // candidate slots per (region, query) of that launch
@@ -137,7 +138,7 @@ struct Scratch {
     bool armed = false;               // `released` has been recorded at least once
     void release_all() {
         for (DevBuf* b : {&q32, &qfrag, &qerr, &mkeys, &floor_q, &cnt, &buf, &sel_rows, &sel_cnt, &bound_approx,
-                          &overflow, &pbuf, &pcnt, &dyn_q, &tl, &tl_tmp, &wtiles, &cand8, &qunion, &qallow})
+                          &overflow, &pbuf, &pcnt, &dyn_q, &tl, &tl_tmp, &wtiles, &cand8, &qunion, &qallow, &qbias})
             b->release();
         if (scanned) (void)hipEventDestroy(scanned);
         if (released) (void)hipEventDestroy(released);
@@ -177,6 +178,7 @@ struct hr_index {
     int shadow8_mode = 1;
     int64_t shadow8_lo = 0;
     double err8 = 0.0;
+    float scale8_max = 0.0f;        // largest row scale of the shadow (device word err8_bits[1]): the bias fold's guard term
     int64_t n_shadow8 = 0;          // shadow-8 FILTER launches issued (diagnostics)
     int last_kc8 = 0;               // candidate depth the most recent shadow-8 scan planned (diagnostics)
     uint32_t* live = nullptr;       // one word per tile
@@ -237,6 +239,7 @@ struct hr_index {
         const void* xnorm = nullptr;
         const void* rows8 = nullptr;
         double err8 = 0.0;
+        float scale8_max = 0.0f;
         const void* pin = nullptr;
         double max_norm2 = 0.0;
         uint64_t buf_gen = 0;

@@ -18,6 +18,8 @@
 //   k_merge      K4/C1  (exact desc, row asc) merge over shards + exactness guard
 //   k_gather     get_by_id de-tiling
 #pragma once
+#include <type_traits>
+
 #include "hr_common.hpp"
 
 namespace hr {
@@ -143,7 +145,8 @@ __global__ __launch_bounds__(256) void k_prep_q(const float* __restrict__ q, int
                                                 int QB, int metric, float* __restrict__ q32,
                                                 uint16_t* __restrict__ qfrag, double* __restrict__ qerr,
                                                 uint32_t* __restrict__ mkeys, int np, uint32_t* __restrict__ cnt,
-                                                float* __restrict__ floor_q, uint32_t* __restrict__ dyn_q) {
+                                                float* __restrict__ floor_q, uint32_t* __restrict__ dyn_q,
+                                                float* __restrict__ qbias = nullptr, double bias_scale = 0.0) {
     const int lane = threadIdx.x & 63;
     const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (b >= Bp) return;
@@ -186,7 +189,7 @@ __global__ __launch_bounds__(256) void k_prep_q(const float* __restrict__ q, int
     double e1 = 0.0, nh = 0.0, qn = 0.0;
     // A-fragment layout [group][S][QB][64 lanes][8]: a group = the QB*32 queries one scan workgroup stages
     const int qg = (b >> 5) / QB, qb = (b >> 5) % QB;
-    auto put = [&](int d, float x) {
+    auto put = [&](int d, float x) -> float {
         const float y = scale ? (float)((double)x * inv) : x;
         q32[(int64_t)b * dpad + d] = y;
         const uint16_t h = quant_mt<MT>(y);
@@ -197,10 +200,11 @@ __global__ __launch_bounds__(256) void k_prep_q(const float* __restrict__ q, int
         e1 += e * e;
         nh += (double)dq * (double)dq;
         qn = qn + (double)y * (double)y;
+        return dq;
     };
+    float dqv[kPrepJ];  // the dequantised elements this lane holds (read by the bias fold below only)
 #pragma unroll
-    for (int j = 0; j < kPrepJ; ++j)
-        if (lane + 64 * j < dpad) put(lane + 64 * j, v[j]);
+    for (int j = 0; j < kPrepJ; ++j) dqv[j] = lane + 64 * j < dpad ? put(lane + 64 * j, v[j]) : 0.0f;
     for (int d = lane + 64 * kPrepJ; d < dpad; d += 64) put(d, src(d));
     e1 = wave_butterfly_sum(e1);
     nh = wave_butterfly_sum(nh);
@@ -210,6 +214,47 @@ __global__ __launch_bounds__(256) void k_prep_q(const float* __restrict__ q, int
         qerr[4 * b + 1] = __builtin_sqrt(nh);
         qerr[4 * b + 2] = qn;
         qerr[4 * b + 3] = 0.0;
+    }
+    // Bias fold of the shadow-8 FILTER (XFrag<F16, I8S>; the sums below read dqv only, so the host passes qbias only
+    // with dpad <= 64 kPrepJ: hr_index.hip, fold8_fits): its MFMAs take the operand
+    // 1152 + s_d (the permuted word, no subtract), so each accumulator starts at -C_q, C_q = 1152 sum_d q^_d, rounded
+    // once to fp32 (qbias; 0 for padding queries).  qerr[4b + 3] bounds what that adds to |approx - exact| at the
+    // largest row scale, bias_scale (DESIGN.md "Exactness guard"), 2^-23 per add as the constant of the plain sum: the chained value
+    // P_k = -C_q + 1152 sum_{d < 16k} q^_d that enters MFMA k may take part in each of that instruction's 16 adds
+    // whatever their order, and so may each of its 16 products, at most 1279 |q^_d|; then the rounding of C_q itself.
+    if constexpr (MT == F16) {
+        if (qbias && dpad <= 64 * kPrepJ) {
+            double sq = 0.0, sa = 0.0;
+#pragma unroll
+            for (int j = 0; j < kPrepJ; ++j) {
+                sq += (double)dqv[j];
+                sa += __builtin_fabs((double)dqv[j]);
+            }
+            sq = wave_butterfly_sum(sq);
+            sa = wave_butterfly_sum(sa);
+            const double C = 1152.0 * sq;
+            const float c32 = (float)-C;
+            // k-step 4j + r holds the elements of lanes 16r .. 16r + 15 at index j
+            double P = (double)c32, chain = 0.0;
+#pragma unroll
+            for (int j = 0; j < kPrepJ; ++j) {
+                if (64 * j >= dpad) continue;  // (wave-uniform)
+                double rs = (double)dqv[j];
+                for (int off = 1; off < 16; off <<= 1) rs += __shfl_xor(rs, off, 64);
+                for (int r = 0; r < 4; ++r) {
+                    const double blk = __shfl(rs, 16 * r, 64);
+                    if (64 * j + 16 * r < dpad) {
+                        chain += __builtin_fabs(P);
+                        P += 1152.0 * blk;
+                    }
+                }
+            }
+            if (lane == 0) {
+                qbias[b] = real ? c32 : 0.0f;
+                qerr[4 * b + 3] =
+                    real ? (0x1p-23 * 16.0 * (chain + 1279.0 * sa) + __builtin_fabs(C + (double)c32)) * (1.0 + 0x1p-10) * bias_scale : 0.0;
+            }
+        }
     }
 }
 
@@ -298,6 +343,11 @@ struct ScanArgs {
     // floats -- each wave refreshes a slice of it and all read it (scan_body: th_row).  0: off, every wave
     // refreshes all its thresholds from the table itself
     int th_off;
+    // shadow-8 scans with the bias fold (scan_body: BF): -C_q per padded query (k_prep_q: qbias), and the byte offset
+    // in LDS (behind the query tile and the threshold row) of the workgroup's copy, QB*32 floats -- every tile's
+    // accumulators start from it
+    const float* qbias;
+    int qb_off;
 };
 
 
@@ -435,6 +485,8 @@ struct XFrag<MT, F32, NT> {
 // bytes 8-15: k-step 2c + 1), each byte the int8 value + 128.  f16 operand by the magic-number form: v_perm_b32
 // puts each byte under 0x64 (the f16 1024 + byte, exact: f16 steps by 1 in [1024, 2048)), one packed f16 subtract of
 // 1152 gives the int8 value, exact -- 4 VALU ops per 4 elements, no per-element cvt.  f16 MFMA only.
+// SUB = false (the bias fold): the permuted words as they are, 1152 + the int8 value -- the subtract is linear, so it
+// leaves the k-loop: sum_d q_d (1152 + s_d) = C_q + sum_d q_d s_d, and the accumulators start at -C_q (k_prep_q: qbias).
 template <bool NT>
 struct XFrag<F16, I8S, NT> {
     static constexpr int kLoads = 1;
@@ -443,12 +495,14 @@ struct XFrag<F16, I8S, NT> {
     __device__ inline void load(const uint8_t* rows, int64_t c, int lane) {
         v = corpus_load<NT>(rows + c * 1024 + lane * 16);
     }
+    template <bool SUB = true>
     __device__ inline u32x4 get(int ks) const {
         typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
         const uint32_t w0 = ks ? v[2] : v[0], w1 = ks ? v[3] : v[1];
         const f16x2 off = {(_Float16)1152.0f, (_Float16)1152.0f};
         auto cv = [&](uint32_t w, uint32_t sel) -> uint32_t {
             const uint32_t m = __builtin_amdgcn_perm(0x64646464u, w, sel);  // bytes 4-7: 0x64, bytes 0-3: w
+            if constexpr (!SUB) return m;
             return __builtin_bit_cast(uint32_t, __builtin_bit_cast(f16x2, m) - off);
         };
         u32x4 o;
@@ -519,9 +573,19 @@ enum { SCAN_SAMPLE = 0, SCAN_FILTER = 1, SCAN_COLLECT = 2 };
 // THL (the shadow-8 FILTER where its threshold row fits in LDS, ScanArgs::th_off): the shared refresh (slice_apply below)
 // instead of the per-wave one.  A kernel of its own: with both refreshes in one body the old one's 64 key registers
 // shape the register allocation of the whole tile loop.
-template <int MT, int DT, int QB, int P, int MODE, bool NT, int TPB, bool LEAN = false, bool QM = false, bool THL = false>
+// BF (the shadow-8 FILTER where the bias row fits in LDS, ScanArgs::qb_off): the bias fold -- the MFMAs take the
+// permuted words (XFrag<F16, I8S>::get<false>) and every tile's accumulators start from the row of -C_q.  The shared
+// refresh is always built with it (its row fits wherever the threshold row does); without it the body is the
+// subtracting one, instruction for instruction what it was.  The SAMPLE keeps the subtract: it scans a few tiles per
+// wave beside or between FILTERs, the fold bought it nothing that could be measured, and three of its folded forms took
+// 2-8 registers more than the subtracting ones (every threshold it leaves is a valid one: the guard's bound is what
+// the FILTER, which scans every row, compared against).
+template <int MT, int DT, int QB, int P, int MODE, bool NT, int TPB, bool LEAN = false, bool QM = false, bool THL = false,
+          bool BF = false>
 __device__ __forceinline__ void scan_body(ScanArgs a) {
     static_assert(!THL || (DT == I8S && !LEAN && !QM && MODE == SCAN_FILTER), "the shared refresh: the shadow-8 FILTER");
+    static_assert(!BF || (DT == I8S && !LEAN && !QM && MODE == SCAN_FILTER), "the bias fold: the shadow-8 FILTER");
+    static_assert(!THL || BF, "the shared refresh is built with the bias fold");
     constexpr bool FILTER = MODE != SCAN_SAMPLE;
     constexpr bool priv = MODE == SCAN_FILTER;
     static_assert(!LEAN || MODE == SCAN_FILTER, "the lean body is a FILTER");
@@ -645,6 +709,13 @@ __device__ __forceinline__ void scan_body(ScanArgs a) {
                                                          lane * 16, c * 16, 0, 0);
         }
     }
+    // the bias fold's row: this thread's word, loaded before the ring's first loads like the DMAs above (the wait
+    // below then covers it and leaves the ring in flight)
+    float bq = 0.0f;
+    if constexpr (BF) {
+        if (tid < QB * 32) bq = a.qbias[tid];
+        asm volatile("" ::: "memory");
+    }
     XFrag<MT, DT, NT> ring[P];
     const bool ring0 = u0 < u1;
     if (ring0) {
@@ -668,6 +739,10 @@ __device__ __forceinline__ void scan_body(ScanArgs a) {
     float* const th_row = (float*)(lds + (TH_ROW ? a.th_off : 0));
     if constexpr (TH_ROW) {
         if (tid < QB * 32) th_row[tid] = -__builtin_inff();
+    }
+    const float* const b_row = (const float*)(lds + (BF ? a.qb_off : 0));
+    if constexpr (BF) {
+        if (tid < QB * 32) ((float*)(lds + a.qb_off))[tid] = bq;
     }
     __syncthreads();
 
@@ -941,10 +1016,31 @@ __device__ __forceinline__ void scan_body(ScanArgs a) {
             asm volatile("" ::: "memory");  // keeps the loads here (the compiler would sink them to their use)
         }
         f32x16 acc[QB];
+        if constexpr (BF) {  // -C_q of the register's query (acc_query): four 16-byte LDS reads per query block
+            typedef float f32x4 __attribute__((ext_vector_type(4)));
+            // this lane's half of the row.  The per-wave-refresh body rebuilds the address at every tile (three VALU
+            // ops) instead of holding it across the k-loop: held, three of its forms took 1-3 registers more than the
+            // subtracting kernels; in the shared-refresh body it is the other way round
+            const float* b_tile = b_row + 4 * half;
+            if constexpr (!THL) {
+                int bofs = (int)(__lane_id() >> 5) * 16 + a.qb_off;
+                asm volatile("" : "+v"(bofs));
+                b_tile = (const float*)(lds + bofs);
+            }
 #pragma unroll
-        for (int qb = 0; qb < QB; ++qb)
+            for (int qb = 0; qb < QB; ++qb)
 #pragma unroll
-            for (int i = 0; i < 16; ++i) acc[qb][i] = 0.0f;
+                for (int j = 0; j < 4; ++j) {
+                    const f32x4 c = *(const f32x4*)(b_tile + qb * 32 + 8 * j);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) acc[qb][4 * j + r] = c[r];
+                }
+        } else {
+#pragma unroll
+            for (int qb = 0; qb < QB; ++qb)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) acc[qb][i] = 0.0f;
+        }
         // row held by this lane's slot (slot swizzle, hr_common.hpp)
         const int rg = slot_row(t, g);
 
@@ -974,7 +1070,10 @@ __device__ __forceinline__ void scan_body(ScanArgs a) {
             for (int i = 0; i < P; ++i) {
                 u32x4 xf[KS];
 #pragma unroll
-                for (int ks = 0; ks < KS; ++ks) xf[ks] = ring[i].get(ks);
+                for (int ks = 0; ks < KS; ++ks) {
+                    if constexpr (DT == I8S) xf[ks] = ring[i].template get<!BF>(ks);
+                    else xf[ks] = ring[i].get(ks);
+                }
                 ring[i].load(a.rows, nc + i, lane);
 #pragma unroll
                 for (int ks = 0; ks < KS; ++ks)
@@ -990,12 +1089,11 @@ __device__ __forceinline__ void scan_body(ScanArgs a) {
         }
 
         if constexpr ((HR_DIAG & 4) != 0) {  // timing build: no epilogue, the accumulators only kept live
-            float s = 0.0f;
+            // (an empty asm per register, no store: pcnt is null in a SAMPLE or COLLECT launch)
 #pragma unroll
             for (int qb = 0; qb < QB; ++qb)
 #pragma unroll
-                for (int i = 0; i < 16; ++i) s += acc[qb][i];
-            if (s == 1234.5f) a.pcnt[wg] = (uint32_t)t;
+                for (int i = 0; i < 16; ++i) asm volatile("" ::"v"(acc[qb][i]));
             ++done;
             if (u + 1 < u_end) {
                 ++u;
@@ -1193,17 +1291,25 @@ __global__ __launch_bounds__(TPB, TPB >= 512 ? 2 : 1) void k_scan_filter(ScanArg
 namespace lds_refresh {
 template <int MT, int DT, int QB, int P, bool NT, int TPB>
 __global__ __launch_bounds__(TPB, TPB >= 512 ? 2 : 1) void k_scan_filter(ScanArgs a) {
-    scan_body<MT, DT, QB, P, SCAN_FILTER, NT, TPB, false, false, true>(a);
+    scan_body<MT, DT, QB, P, SCAN_FILTER, NT, TPB, false, false, true, true>(a);
 }
 }  // namespace lds_refresh
+// the shadow-8 per-wave-refresh FILTER with the bias fold (scan_body: BF), named like the shared refresh's
+namespace bias_fold {
+template <int MT, int DT, int QB, int P, bool NT, int TPB>
+__global__ __launch_bounds__(TPB, TPB >= 512 ? 2 : 1) void k_scan_filter(ScanArgs a) {
+    scan_body<MT, DT, QB, P, SCAN_FILTER, NT, TPB, false, false, false, true>(a);
+}
+}  // namespace bias_fold
 template <int MT, int DT, int QB, int P, bool NT, int TPB>
 __global__ __launch_bounds__(TPB, TPB >= 512 ? 2 : 1) void k_scan_collect(ScanArgs a) {
     scan_body<MT, DT, QB, P, SCAN_COLLECT, NT, TPB>(a);
 }
-template <int MT, int DT, int QB, int P, int MODE, bool NT, int TPB, bool QM = false, bool THL = false>
+template <int MT, int DT, int QB, int P, int MODE, bool NT, int TPB, bool QM = false, bool THL = false, bool BF = false>
 constexpr auto scan_kernel() {
     if constexpr (MODE == SCAN_SAMPLE) return &k_scan_sample<MT, DT, QB, P, NT, TPB, QM>;
     else if constexpr (MODE == SCAN_FILTER && THL) return &lds_refresh::k_scan_filter<MT, DT, QB, P, NT, TPB>;
+    else if constexpr (MODE == SCAN_FILTER && BF) return &bias_fold::k_scan_filter<MT, DT, QB, P, NT, TPB>;
     else if constexpr (MODE == SCAN_FILTER) return &k_scan_filter<MT, DT, QB, P, NT, TPB, QM>;
     else return &k_scan_collect<MT, DT, QB, P, NT, TPB>;
 }
@@ -1216,7 +1322,8 @@ template <int MT, int DT, int QB>
 __global__ __launch_bounds__(256) void k_debug_approx(const uint8_t* __restrict__ rows, const uint16_t* __restrict__ qfrag,
                                                       int S, int64_t n_tiles, const float* __restrict__ xnorm,
                                                       float* __restrict__ out,
-                                                      const float* __restrict__ rscale = nullptr) {
+                                                      const float* __restrict__ rscale = nullptr,
+                                                      const float* __restrict__ qbias = nullptr) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     stage_lds((u32x4*)lds, (const u32x4*)qfrag, S * QB * 64);
     __syncthreads();
@@ -1225,21 +1332,33 @@ __global__ __launch_bounds__(256) void k_debug_approx(const uint8_t* __restrict_
     if (t >= n_tiles) return;
     const u32x4* qs = (const u32x4*)lds;
     f32x16 acc[QB];
+    // qbias (8-bit shadow): the scan's bias fold -- the same start value and the same unsubtracted operand
+    const bool fold = DT == I8S && qbias != nullptr;
 #pragma unroll
     for (int qb = 0; qb < QB; ++qb)
 #pragma unroll
-        for (int i = 0; i < 16; ++i) acc[qb][i] = 0.0f;
+        for (int i = 0; i < 16; ++i) acc[qb][i] = fold ? qbias[acc_query(qb, i, lane >> 5)] : 0.0f;
     constexpr int KS = XFrag<MT, DT>::kSteps;
-    for (int s = 0; s < S / KS; ++s) {
-        XFrag<MT, DT> x;
-        x.load(rows, t * (S / KS) + s, lane);
+    auto dots = [&](auto sub) {
+        for (int s = 0; s < S / KS; ++s) {
+            XFrag<MT, DT> x;
+            x.load(rows, t * (S / KS) + s, lane);
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            const u32x4 xf = x.get(ks);
+            for (int ks = 0; ks < KS; ++ks) {
+                u32x4 xf;
+                if constexpr (DT == I8S) xf = x.template get<decltype(sub)::value>(ks);
+                else xf = x.get(ks);
 #pragma unroll
-            for (int qb = 0; qb < QB; ++qb)
-                acc[qb] = mfma32<MT>(qs[((s * KS + ks) * QB + qb) * 64 + lane], xf, acc[qb]);
+                for (int qb = 0; qb < QB; ++qb)
+                    acc[qb] = mfma32<MT>(qs[((s * KS + ks) * QB + qb) * 64 + lane], xf, acc[qb]);
+            }
         }
+    };
+    if constexpr (DT == I8S) {
+        if (fold) dots(std::false_type{});
+        else dots(std::true_type{});
+    } else {
+        dots(std::true_type{});
     }
     const int64_t ncol = n_tiles * 32;
     const int rg = slot_row(t, lane & 31);
