@@ -241,6 +241,45 @@ int hr_index_search_range(hr_index* h, const float* q, int B, const float* min_s
 int hr_index_search_range_device(hr_index* h, const float* q_dev, int B, const float* min_score_dev, int max_hits,
                                  const uint64_t* row_mask_dev, float* scores_out_dev, int64_t* rows_out_dev,
                                  int64_t* counts_out_dev, void* stream);
+/* Search by example: queries built on the device from stored rows ("more like this chunk": Qdrant's recommend,
+ * Weaviate's nearObject, Pinecone's query by id; tests/examples_ref.py restates it bit for bit).
+ * A batch of B queries.  Query b has an optional fp32 base vector q[b] (q = NULL: none) and m_b = ex_off[b + 1] -
+ * ex_off[b] examples: the stored rows ex_rows[e] with the fp32 weights ex_weights[e], e in [ex_off[b], ex_off[b + 1]);
+ * a negative weight is a negative example.  ex_off holds B + 1 non-decreasing offsets; the three lists are always
+ * HOST arrays (they are ids, not vectors), also in the device forms.
+ * Built query, per component d < dim, in fp64: acc = (double)q[b][d], or 0.0 without q; then for e in list order
+ * acc = acc + (double)w_e * (double)x_e[d], x_e[d] the stored element of row ex_rows[e] widened to fp32 (the bits
+ * hr_index_get_rows returns); built[b][d] = (float)acc, round to nearest even.  The product of two fp32 values is
+ * exact in fp64, so one rounding per example and one cast: a fused multiply-add gives the same bits.
+ * hr_index_build_queries writes the B built queries row-major (B * dim floats); its device form reads q_dev and writes
+ * q_out_dev in device memory, and its output may feed any *_device search (range, MMR, collapsed, masks).
+ * hr_index_search_examples: the answer of query b is what hr_index_search(h, built[b], 1, k, row_mask) gives with the
+ * rows of b's example list removed from the candidates -- the same processing of the query (cosine: normalised by
+ * the canonical query prep), the same order (canonical fp64 score desc, row asc), the same fp32 score bits; slots past
+ * the remaining live, allowed rows hold -inf / -1.  Positive and negative examples are both excluded; a row listed
+ * twice adds its weights and is excluded once; a row the mask forbids is still a legal example.  flags = HR_EX_KEEP
+ * switches the exclusion off: the answer is then hr_index_search of the built queries, bit for bit.
+ * Mechanism: one search of the batch for K' = k + M rows, M = the largest m_b (0 with HR_EX_KEEP), then the examples
+ * dropped from every list on the device.  The top-K' of the allowed rows minus at most m_b of them contains the
+ * top-k of the remainder, so the result is exact and there is no fallback stage of its own; K' > HR_MAX_K takes the
+ * exhaustive exact pass of hr_index_search.
+ * Limits: 0 <= m_b <= HR_EX_MAX; m_b = 0 without q, an example row outside [0, n) or removed, a NaN or infinite
+ * weight: HR_E_INVALID, all checked on the host before any kernel is launched.  A built query that comes out all
+ * zero (weights that cancel) is legal: it scores 0 everywhere and the order is row ascending.  k >= 1, any B >= 1,
+ * every dtype and metric; an empty index returns padding; a multi-device handle: HR_E_UNSUPPORTED.  The device
+ * forms are ordered after the work queued on `stream` and return with it idle. */
+#define HR_EX_MAX 32           /* examples of one query */
+enum { HR_EX_KEEP = 1 };       /* hr_index_search_examples flags: the examples stay candidates */
+int hr_index_build_queries(hr_index* h, const int64_t* ex_rows, const float* ex_weights, const int64_t* ex_off, int B,
+                           const float* q /* B*dim or NULL */, float* q_out /* B*dim */);
+int hr_index_build_queries_device(hr_index* h, const int64_t* ex_rows, const float* ex_weights, const int64_t* ex_off,
+                                  int B, const float* q_dev, float* q_out_dev, void* stream);
+int hr_index_search_examples(hr_index* h, const float* q, const int64_t* ex_rows, const float* ex_weights,
+                             const int64_t* ex_off, int B, int k, int flags, const uint64_t* row_mask,
+                             float* scores_out, int64_t* rows_out);
+int hr_index_search_examples_device(hr_index* h, const float* q_dev, const int64_t* ex_rows, const float* ex_weights,
+                                    const int64_t* ex_off, int B, int k, int flags, const uint64_t* row_mask_dev,
+                                    float* scores_out_dev, int64_t* rows_out_dev, void* stream);
 int hr_index_size(hr_index* h, int64_t* n_out, int64_t* n_live_out);
 /* Shape of a handle (e.g. one returned by hr_index_load): dim, storage dtype, metric, devices. */
 int hr_index_info(hr_index* h, int* dim_out, int* dtype_out, int* metric_out, int* n_dev_out);

@@ -2424,8 +2424,8 @@ int index_prep_exact(hr_index* h, const float* q_dev, int B, hipStream_t st, con
 // Exact top-m of every query over the whole shard into device records out_dev[B][m] (local row + row_offset;
 // -inf / -1 padding past the live, allowed rows): canonical fp64 score of every row + stable radix sort, the same
 // arithmetic and (score desc, row asc) order as the scan path.  One corpus pass and one n-row sort per query.
-static int index_exact_dev(hr_index* h, const float* q_dev, int B, int m, const uint64_t* mask_dev, int64_t row_offset,
-                           Cand* out_dev, hipStream_t st) {
+int index_exact_dev(hr_index* h, const float* q_dev, int B, int m, const uint64_t* mask_dev, int64_t row_offset,
+                    Cand* out_dev, hipStream_t st) {
     const float* q32 = nullptr;
     std::vector<double> qerr;
     if (int rc = index_prep_exact(h, q_dev, B, st, &q32, &qerr)) return rc;
@@ -2938,6 +2938,7 @@ extern "C" void hr_index_destroy(hr_index* h) {
     collapse_free(h);
     range_free(h);
     mmr_free(h);
+    examples_free(h);
     (void)hipDeviceSynchronize();  // pipelined batches may still run on caller streams
     for (auto& g : h->sync_graphs)
         if (g.exec) (void)hipGraphExecDestroy(g.exec);

@@ -314,6 +314,11 @@ struct hr_index {
     int64_t n_range_scans = 0;                    // window-scan launches (one per chunk of queries)
     DevBuf rng_wtiles;                            // diagnostics: tiles each wave of the most recent window scan scanned
     int64_t rng_waves = 0;                        // ... and how many waves that launch had (all query groups)
+    // ---- search by example (hr_examples.hip): every buffer allocated by the first call that needs it.  ex_list: one
+    // call's example lists as one block (offsets | rows | weights), packed in ex_host and copied once
+    DevBuf ex_list, ex_qin, ex_q, ex_mask, ex_s, ex_r, ex_cand, ex_out;  // lists, host base queries, built queries,
+                                                                        // host mask, K' results / records, host results
+    std::vector<uint8_t> ex_host;
 };
 
 // an internal stream of h: on h's CU mask when one is set (priority is then not available), else high priority or
@@ -391,6 +396,10 @@ int range_floors(const double* qerr, const float* min_score, int B, int Bp, doub
                  int metric, float* floor_q, hipStream_t st);
 void range_free(hr_index* h);  // hr_index_destroy's part
 void mmr_free(hr_index* h);  // hr_mmr.hip: hr_index_destroy's part
+void examples_free(hr_index* h);  // hr_examples.hip: hr_index_destroy's part
+// the exhaustive exact pass of a k > HR_MAX_K search into device records out_dev[B][m] (hr_index.hip)
+int index_exact_dev(hr_index* h, const float* q_dev, int B, int m, const uint64_t* mask_dev, int64_t row_offset,
+                    Cand* out_dev, hipStream_t st);
 int launch_merge(int device, const Cand* cand, const double* bounds, int G, int B, int kc, int k, float* s_out,
                  int64_t* r_out, double* kth_out, int32_t* fail_out, hipStream_t st, int64_t cstride = 0,
                  int64_t bstride = 0);

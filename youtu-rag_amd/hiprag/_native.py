@@ -8,6 +8,7 @@ constructors raise.
 from __future__ import annotations
 
 import ctypes
+import itertools
 import os
 import threading
 
@@ -21,6 +22,8 @@ METRICS = {"cosine": 0, "ip": 1, "dot": 1, "euclidean": 2, "l2": 2}
 HR_MAX_K = 128   # include/hiprag.h
 HR_MAX_KC = 256
 HR_RANGE_MAX_HITS = 65536  # largest max_hits of search_range
+HR_EX_MAX = 32  # examples of one query of search_examples
+HR_EX_KEEP = 1  # search_examples flag: the examples stay candidates
 HR_CREATE_NO_SHADOWS = 1
 HR_LEX_TERM_BITS = 22    # term id = crc32(token) % 2**22
 HR_LEX_MAX_QTERMS = 64
@@ -64,6 +67,8 @@ EXPORTS = [
     "hr_index_search_mmr", "hr_index_search_mmr_device", "hr_index_set_mmr_timing", "hr_index_mmr_last_ms",
     "hr_index_search_range", "hr_index_search_range_device", "hr_index_range_stats",
     "hr_index_range_wave_tiles",
+    "hr_index_build_queries", "hr_index_build_queries_device", "hr_index_search_examples",
+    "hr_index_search_examples_device",
 ]
 
 _lib = None
@@ -225,6 +230,10 @@ def load_library(path: str | None = None):
             "hr_index_search_range_device": [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp],
             "hr_index_range_stats": [vp, vp],
             "hr_index_range_wave_tiles": [vp, vp, i32, vp],
+            "hr_index_build_queries": [vp, vp, vp, vp, i32, vp, vp],
+            "hr_index_build_queries_device": [vp, vp, vp, vp, i32, vp, vp, vp],
+            "hr_index_search_examples": [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp],
+            "hr_index_search_examples_device": [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp],
         }
         for name, args in sig.items():
             if p != (path or LIB_PATH) and not hasattr(L, name):
@@ -598,6 +607,84 @@ class NativeIndex:
         n = ctypes.c_int(0)
         _check(self.lib.hr_index_range_wave_tiles(self._h, _ptr(out), int(cap), ctypes.byref(n)))
         return out[: n.value].copy()
+
+    # -- search by example (hr_examples.hip): queries built on the device from stored rows
+    @staticmethod
+    def _example_lists(examples, weights):
+        """(rows int64, weights fp32, offsets int64) of a list of row lists; default weights 1 / m_b, computed in
+        float64 and cast to fp32."""
+        examples = list(examples)
+        lens = [len(e) for e in examples]  # (one pass over flat Python lists: this runs before every launch)
+        off = np.zeros(len(lens) + 1, np.int64)
+        np.cumsum(lens, out=off[1:])
+        tot = int(off[-1])
+        rows = np.fromiter(itertools.chain.from_iterable(examples), np.int64, count=tot)
+        if weights is None:
+            w = np.repeat(np.float64(1.0) / np.maximum(np.asarray(lens, np.float64), 1.0), lens).astype(np.float32)
+        else:
+            weights = list(weights)
+            if [len(x) for x in weights] != lens:
+                raise ValueError("weights must have the shape of examples")
+            w = np.fromiter(itertools.chain.from_iterable(weights), np.float64, count=tot).astype(np.float32)
+        return rows, w, off
+
+    def _base_queries(self, q, B):
+        if q is None:
+            return None
+        q = np.ascontiguousarray(q, np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.shape != (B, self.dim):
+            raise ValueError(f"base queries must be ({B}, {self.dim}) float32")
+        return q
+
+    def build_queries(self, examples, weights=None, q=None) -> np.ndarray:
+        """The queries search_examples searches with (hr_index_build_queries): per entry of ``examples`` (a list of
+        row lists) ``q[b] + sum of weights[b][e] * stored row examples[b][e]`` accumulated in float64 in list order
+        and cast to fp32.  ``weights``: the same shape as ``examples``, default 1 / len(examples[b]); ``q``: optional
+        (B, dim) base vectors."""
+        rows, w, off = self._example_lists(examples, weights)
+        B = len(off) - 1
+        q = self._base_queries(q, B)
+        out = np.empty((B, self.dim), np.float32)
+        _check(self.lib.hr_index_build_queries(self._h, _ptr(rows), _ptr(w), _ptr(off), B, _ptr(q), _ptr(out)))
+        return out
+
+    def build_queries_device(self, examples, q_out_ptr: int, weights=None, q_ptr: int = 0, stream: int = 0) -> None:
+        """build_queries() with the base vectors and the output in device memory (the lists stay host lists); the
+        output can feed any ``*_device`` search.  Ordered after ``stream``, which is idle on return."""
+        rows, w, off = self._example_lists(examples, weights)
+        _check(self.lib.hr_index_build_queries_device(self._h, _ptr(rows), _ptr(w), _ptr(off), len(off) - 1,
+                                                      ctypes.c_void_p(q_ptr or None), ctypes.c_void_p(q_out_ptr),
+                                                      ctypes.c_void_p(stream or None)))
+
+    def search_examples(self, examples, k: int, weights=None, q=None, mask: np.ndarray | None = None,
+                        keep: bool = False) -> tuple[np.ndarray, np.ndarray]:
+        """"More like these rows" (hr_index_search_examples): search() of build_queries(examples, weights, q) with
+        every query's own examples -- positive and negative -- removed from its candidates, exactly; ``keep=True``
+        leaves them in (then it is search() of the built queries, bit for bit)."""
+        rows, w, off = self._example_lists(examples, weights)
+        B = len(off) - 1
+        q = self._base_queries(q, B)
+        if int(k) <= 0:  # (before the output arrays are sized by it)
+            raise ValueError("k must be positive")
+        s = np.empty((B, int(k)), np.float32)
+        r = np.empty((B, int(k)), np.int64)
+        m = self._mask_words(mask)
+        _check(self.lib.hr_index_search_examples(self._h, _ptr(q), _ptr(rows), _ptr(w), _ptr(off), B, int(k),
+                                                 HR_EX_KEEP if keep else 0, _ptr(m), _ptr(s), _ptr(r)))
+        return s, r
+
+    def search_examples_device(self, examples, k: int, scores_ptr: int, rows_ptr: int, weights=None, q_ptr: int = 0,
+                               mask_ptr: int = 0, keep: bool = False, stream: int = 0) -> None:
+        """search_examples() with base vectors, mask and outputs in device memory (the lists stay host lists);
+        ordered after ``stream``, which is idle on return."""
+        rows, w, off = self._example_lists(examples, weights)
+        _check(self.lib.hr_index_search_examples_device(self._h, ctypes.c_void_p(q_ptr or None), _ptr(rows), _ptr(w),
+                                                        _ptr(off), len(off) - 1, int(k), HR_EX_KEEP if keep else 0,
+                                                        ctypes.c_void_p(mask_ptr or None),
+                                                        ctypes.c_void_p(scores_ptr), ctypes.c_void_p(rows_ptr),
+                                                        ctypes.c_void_p(stream or None)))
 
     def search_device(self, q_ptr: int, B: int, k: int, scores_ptr: int, rows_ptr: int, mask_ptr: int = 0,
                       stream: int = 0) -> None:

@@ -326,6 +326,24 @@ class VectorRetriever(BaseRetriever):
                    for pos, (chunk, score) in enumerate(found.hits)]
         return await self._finish(query, results, int(limit))
 
+    async def retrieve_similar(self, chunk_id_or_ids, top_k: int | None = None, filters: dict | None = None,
+                               negative_ids=None, query: str | None = None) -> list[RetrievalResult]:
+        """"More like this chunk": the store's search by example over the stored vectors of ``chunk_id_or_ids`` (one
+        id or a list), steered away from ``negative_ids``; ``query`` is embedded and used as the base vector
+        (relevance feedback on top of the question).  The named chunks are never returned.  Ranks (1-based, before the
+        threshold), ``config.similarity_threshold`` and the final cut as in retrieve(); the reranker needs a text to
+        rank against, so it applies only with ``query``."""
+        search_similar = getattr(self.vector_store, "search_similar", None)
+        if search_similar is None:
+            raise NotImplementedError(f"{type(self.vector_store).__name__} has no search by example")
+        top_k = top_k or self.config.top_k
+        rerank = self.reranker is not None and query is not None
+        qv = await self.embedder.embed_query(query) if query is not None else None
+        hits = await search_similar(chunk_id_or_ids, top_k=top_k * 2 if rerank else top_k, filters=filters,
+                                    negative_ids=negative_ids, query_embedding=qv)
+        results = self._to_results(hits, self.config.similarity_threshold)
+        return await self._finish(query, results, top_k) if rerank else results[:top_k]
+
     async def batch_retrieve(self, queries: list[str], top_k: int | None = None, **kwargs
                              ) -> list[list[RetrievalResult]]:
         return [await self.retrieve(query=q, top_k=top_k, **kwargs) for q in queries]

@@ -65,6 +65,13 @@ not the best k of a guessed ``top_k`` (hr_index_search_range).  Ea
 total)``: the first ``max_hits`` hits, best first, and the count whatever ``max_hits`` is (``truncated``: the list was
 cut).  Range calls do not go through the micro-batcher; the single-query form runs in a worker thread.
 
+Search by example (``search_similar_batch(positive_ids, negative_ids, top_k)`` / ``await search_similar(chunk_ids)``):
+"more like these chunks" -- the query is built from the STORED vectors of the named chunks, ``pos_weight / |P|`` each
+for the positives and ``-neg_weight / |N|`` for the negatives on top of an optional query embedding, on the GPU, and
+the named chunks never appear in their own answer (hr_index_search_examples).  An index without a native
+``search_examples`` (several devices, IVF_FLAT) gets the same arithmetic composed on the host from ``get_rows`` and
+``search``.  Calls do not go through the micro-batcher; the single-query form runs in a worker thread.
+
 ``index_type: "IVF_FLAT"`` (any letter case; single device, cosine / dot): the index is an ``IvfStoreIndex``
 (ivf_store.py) -- the same exact index plus an IVF replica that answers searches once ``ivf_train_rows`` live rows
 are stored (``index_params``: nlist, nprobe, ivf_train_rows = 64 nlist, ivf_seed).  It comes in through the
@@ -142,6 +149,43 @@ def _assemble_results_py(C, R, rec_l, meta_l, score_l, per_q, embs, ks, ths, unt
 logger = logging.getLogger(__name__)
 
 _METRIC = {"cosine": "cosine", "dot": "ip", "euclidean": "l2"}
+
+
+def build_queries_host(idx, examples, weights, q=None) -> np.ndarray:
+    """hr_index_build_queries restated over ``idx.get_rows``: per query ``q[b]`` (or 0) plus, in list order,
+    ``float64(fp32 weight) * float64(stored row)``, accumulated in float64 and cast to fp32 once."""
+    flat = [int(r) for e in examples for r in e]
+    x = np.asarray(idx.get_rows(flat), np.float32).astype(np.float64) if flat else None
+    dim = x.shape[1] if flat else np.asarray(q).shape[-1]
+    acc = np.zeros((len(examples), dim), np.float64)
+    if q is not None:
+        acc += np.asarray(q, np.float32).reshape(len(examples), dim)
+    pos = 0
+    for b, (e, w) in enumerate(zip(examples, weights)):
+        for j in range(len(e)):
+            acc[b] = acc[b] + np.float64(np.float32(w[j])) * x[pos]
+            pos += 1
+    with np.errstate(over="ignore"):
+        return acc.astype(np.float32)
+
+
+def search_examples_host(idx, examples, k: int, weights, q=None, mask=None, keep: bool = False):
+    """NativeIndex.search_examples for an index without one, with the same bits wherever ``idx.search`` is exact:
+    build_queries_host, ONE ``idx.search`` for k + (the longest example list) rows, every query's own examples dropped
+    from its list, the first k kept, -inf / -1 after them."""
+    examples = [[int(r) for r in e] for e in examples]
+    built = build_queries_host(idx, examples, weights, q)
+    depth = 0 if keep else max((len(e) for e in examples), default=0)
+    s, r = idx.search(built, int(k) + depth, mask)
+    out_s = np.full((len(examples), int(k)), -np.inf, np.float32)
+    out_r = np.full((len(examples), int(k)), -1, np.int64)
+    for b, e in enumerate(examples):
+        stay = r[b] >= 0
+        if not keep:
+            stay &= ~np.isin(r[b], e)
+        sel = np.nonzero(stay)[0][: int(k)]
+        out_s[b, : len(sel)], out_r[b, : len(sel)] = s[b][sel], r[b][sel]
+    return out_s, out_r
 
 
 class RangeHits(NamedTuple):
@@ -1371,6 +1415,112 @@ class HipVectorStore(BaseVectorStore):
         if raw is None:
             return RangeHits([], int(counts[0]))
         return RangeHits(self._assemble(prep, (raw, tables))[0], int(counts[0]))
+
+    # -- search by example (hr_index_search_examples): "more like these chunks"
+    def _prep_similar(self, positive_ids, negative_ids, top_k: int, filters, query_embeddings, pos_weight, neg_weight):
+        """(example rows, fp32 weights, base queries or None, top_k, filters) of a search by example, every limit
+        checked and every id resolved: a bad request fails here, before any native call."""
+        def ids_of(entry):
+            if entry is None:
+                return []
+            return [entry] if isinstance(entry, str) else list(entry)
+
+        pos = [ids_of(p) for p in positive_ids]
+        B = len(pos)
+        neg = [[] for _ in range(B)] if negative_ids is None else [ids_of(n) for n in negative_ids]
+        if len(neg) != B:
+            raise ValueError(f"{len(neg)} negative lists for {B} queries")
+        pw, nw = float(pos_weight), float(neg_weight)
+        if not (np.isfinite(pw) and np.isfinite(nw)):
+            raise ValueError("pos_weight and neg_weight must be finite")
+        q = None
+        if query_embeddings is not None:
+            q = np.asarray(query_embeddings, dtype=np.float32)
+            if q.ndim == 1:
+                q = q[None, :]
+            if q.shape[0] != B:
+                raise ValueError(f"{q.shape[0]} query embeddings for {B} queries")
+            dim = self.dim
+            if dim is not None and q.shape[1] != dim:
+                raise ValueError(f"query dim {q.shape[1]} != collection dim {dim}")
+        if isinstance(filters, (list, tuple)):  # one where-clause (or None) per query
+            filters = list(filters)
+            if len(filters) != B:
+                raise ValueError(f"{len(filters)} filters for {B} queries")
+            if len({_filter_key(f) for f in filters}) == 1:
+                filters = filters[0] or None
+        examples, weights = [], []
+        with self._lock:
+            for P_, N_ in zip(pos, neg):
+                if len(P_) + len(N_) > _native.HR_EX_MAX:
+                    raise ValueError(f"a query takes at most {_native.HR_EX_MAX} example chunks "
+                                     f"(got {len(P_) + len(N_)})")
+                if not P_ and not N_ and q is None:
+                    raise ValueError("a query without example chunks needs a query embedding")
+                rows = []
+                for cid in P_ + N_:
+                    row = self._id_to_row.get(cid)
+                    if row is None:
+                        raise ValueError(f"unknown chunk id {cid!r}")
+                    rows.append(int(row))
+                examples.append(rows)
+                w = [np.float64(pw) / len(P_) for _ in P_] + [-np.float64(nw) / len(N_) for _ in N_]
+                weights.append([np.float32(v) for v in w])
+        return examples, weights, q, int(top_k), filters
+
+    def _run_similar(self, prep):
+        """The search by example under the store lock, as _run_search: ((scores, rows) or None, tables).  Natively
+        where the index can, else composed on the host; a per-query filter list runs one call per distinct clause."""
+        examples, weights, q, top_k, filters = prep
+        B = len(examples)
+        with self._lock:  # ordered against mutations
+            tables = (self._records, self._metas, self._epoch)
+            idx, n_live = self._index, self.count_sync()
+            if idx is None or n_live == 0 or top_k <= 0 or B == 0:
+                return None, tables
+            k = min(top_k, n_live)
+            native = hasattr(idx, "search_examples") and len(getattr(idx, "devices", (0,))) == 1
+
+            def call(sel, bitmap):
+                ex, w = [examples[i] for i in sel], [weights[i] for i in sel]
+                qs = None if q is None else q[sel]
+                if native:
+                    return idx.search_examples(ex, k, w, qs, bitmap)
+                return search_examples_host(idx, ex, k, w, qs, bitmap)
+
+            if not isinstance(filters, list):
+                return call(np.arange(B), self.filter_bitmap(filters)), tables
+            clauses, clause_of, bitmaps = self._distinct_filters(filters)
+            scores = np.full((B, k), -np.inf, np.float32)
+            rows_out = np.full((B, k), -1, np.int64)
+            for c in range(len(clauses)):
+                sel = np.nonzero(clause_of == c)[0]
+                scores[sel], rows_out[sel] = call(sel, bitmaps[c])
+                self.grouped_launches += 1
+            return (scores, rows_out), tables
+
+    def search_similar_batch(self, positive_ids, negative_ids=None, top_k: int = 5, filters=None,
+                             query_embeddings=None, pos_weight: float = 1.0, neg_weight: float = 1.0
+                             ) -> list[list[tuple[Chunk, float]]]:
+        """"More like these chunks", one query per entry of ``positive_ids`` (a chunk id or a list of them; matching
+        entries of ``negative_ids``: chunks to steer away from; ``query_embeddings``: optional base vectors, one per
+        query).  The query is ``base + pos_weight * mean(stored positives) - neg_weight * mean(stored negatives)``
+        (weights ``pos_weight / |P|`` and ``-neg_weight / |N|``, float64 then fp32), searched exactly; the named chunks
+        are never among their own hits.  ``filters``: one where-clause, or a list with one (or None) per query.  An
+        unknown chunk id raises ValueError naming it; a query takes at most 32 example chunks."""
+        prep = self._prep_similar(positive_ids, negative_ids, top_k, filters, query_embeddings, pos_weight, neg_weight)
+        return self._assemble(prep, self._run_similar(prep))
+
+    async def search_similar(self, chunk_ids, top_k: int = 5, filters: dict[str, Any] | None = None, *,
+                             negative_ids=None, query_embedding=None) -> list[tuple[Chunk, float]]:
+        """One search by example -- ``chunk_ids``: a chunk id or a list of them -- off the event loop."""
+        ids = [chunk_ids] if isinstance(chunk_ids, str) else list(chunk_ids)
+        neg = negative_ids
+        if neg is not None:
+            neg = [[neg] if isinstance(neg, str) else list(neg)]
+        qe = None if query_embedding is None else np.asarray(query_embedding, np.float32).reshape(1, -1)
+        prep = self._prep_similar([ids], neg, top_k, filters, qe, 1.0, 1.0)  # checked here: a bad request fails alone
+        return self._assemble(prep, await asyncio.to_thread(self._run_similar, prep))[0]
 
     def get_by_id_sync(self, chunk_id: str) -> Chunk | None:
         with self._lock:
