@@ -280,6 +280,60 @@ int hr_index_search_examples(hr_index* h, const float* q, const int64_t* ex_rows
 int hr_index_search_examples_device(hr_index* h, const float* q_dev, const int64_t* ex_rows, const float* ex_weights,
                                     const int64_t* ex_off, int B, int k, int flags, const uint64_t* row_mask_dev,
                                     float* scores_out_dev, int64_t* rows_out_dev, void* stream);
+/* Fused multi-query search: several ranked lists per question -- rewritten queries, HyDE, sub-questions, widened
+ * filter scopes -- fused on the device by reciprocal rank or by the largest score (Elasticsearch's rrf retriever,
+ * Qdrant's query with fusion: rrf, LangChain's MultiQueryRetriever / EnsembleRetriever; the reference's agent merges
+ * its searches by max score on the host, meta_retrieval_toolkit.py:619-627; tests/fused_ref.py restates all of it).
+ * hr_fuse_lists -- the fusion alone, on lists that already lie in device memory.
+ * Input: Q = grp_off[G] ranked lists of P slots each, in the format every search writes: slot p of list i holds
+ * rows[i * P + p] and scores[i * P + p]; a row of -1 (any negative row) is padding and never an entry; the rows of one
+ * list are distinct.  Group g owns the lists [grp_off[g], grp_off[g + 1]): its members, m_g of them.  grp_off (G + 1
+ * offsets, grp_off[0] = 0) and weights (Q values, or NULL) are always HOST arrays, like ex_off above.
+ * Semantics, per group, over the distinct rows r that appear in any of its members:
+ *   HR_FUSE_RRF  fused(r) starts at 0.0 in fp64; then, for the members i in member order that hold r, at 1-based
+ *                position p_i: fused = fused + (double)w_i / (rrf_k + (double)p_i), w_i = weights[i], 1.0f when
+ *                weights is NULL.  One division and one addition per term, each rounded once, no reassociation (a
+ *                fused multiply-add cannot arise).  With two members and NULL weights this is the retriever's
+ *                rrf_fuse bit for bit, order included.
+ *   HR_FUSE_MAX  fused(r) is the largest fp32 score among the members holding r, widened to double; a NaN score
+ *                counts as -inf; weights must be NULL (else HR_E_INVALID).
+ *   order        fused descending, then row ascending (-0.0 and 0.0 are equal): the project's order everywhere.  The
+ *                first min(k, distinct rows) are written; the remaining slots hold -inf / -1 / 0.
+ *   members_out  (may be NULL) bit j is set iff member grp_off[g] + j holds the row: which rewrite found the chunk.
+ * Limits: 1 <= m_g <= HR_FUSE_MAX_MEMBERS (an empty group: HR_E_INVALID); 1 <= k <= P <= HR_MAX_K; G >= 1; rrf_k
+ * finite and >= 0; weights finite (zero and negative ones are legal); mode one of the two values -- all checked on
+ * the host before any launch.  One workgroup per group sorts the group's <= 2048 entries in LDS; no floating-point
+ * atomics, nothing that depends on scheduling.  Ordered after the work queued on `stream` of `device`; returns with
+ * it idle.
+ * hr_index_search_fused -- the members searched and fused in one call.  q: Q query vectors; member i's pool is exactly
+ * what hr_index_search_masks(h, q_i, 1, fetch_k, masks, D, mask_stride, mask_of + i, ...) returns for it (D = 0:
+ * hr_index_search, and mask_of may be NULL): the same rows, order and fp32 score bits.  All Q members go through the
+ * scan as one batch (the single-mask search when every member names the same bitmap: identical by contract), the
+ * pools are fused by hr_fuse_lists with P = fetch_k and never leave the device.
+ * fetch_k = 0 is the default: min(HR_MAX_K, max(4 k, 50)) for RRF (the HybridRetriever's depth), k for MAX; else
+ * k <= fetch_k <= HR_MAX_K; 1 <= k <= HR_MAX_K.
+ * RRF is a function of the rank window (Elasticsearch's rank_window_size): a deeper fetch_k can change the answer.
+ * MAX with fetch_k >= k returns the corpus-wide k largest values of max_i score_i(r): a row outside every pool scores
+ * no more than each pool's last entry; only the choice among rows with EQUAL fp32 fused score at the cut is
+ * pool-defined.  With one member, RRF (any positive weight) returns that member's top-k rows in order.  The pools are
+ * exact and the answer a function of them: no fallback stage of its own.
+ * An empty index returns padding; a multi-device handle: HR_E_UNSUPPORTED; the mask rules are those of
+ * hr_index_search_masks.  The device form takes every vector, mask (mask_of included) and output pointer in device
+ * memory, is ordered after the work queued on `stream` and returns with it idle. */
+#define HR_FUSE_MAX_MEMBERS 16 /* lists of one group */
+enum { HR_FUSE_RRF = 0, HR_FUSE_MAX = 1 };
+int hr_fuse_lists(int device, const int64_t* rows_dev /* Q*P */, const float* scores_dev /* Q*P */, int P,
+                  const int64_t* grp_off /* G+1, HOST */, const float* weights /* Q or NULL, HOST */, int G, int k,
+                  int mode, double rrf_k, double* fused_out_dev /* G*k */, int64_t* rows_out_dev /* G*k */,
+                  uint32_t* members_out_dev /* G*k, nullable */, void* stream);
+int hr_index_search_fused(hr_index* h, const float* q /* Q*dim */, const int64_t* grp_off, const float* weights, int G,
+                          int k, int fetch_k, int mode, double rrf_k, const uint64_t* masks, int D,
+                          int64_t mask_stride, const int32_t* mask_of /* Q */, double* fused_out, int64_t* rows_out,
+                          uint32_t* members_out);
+int hr_index_search_fused_device(hr_index* h, const float* q_dev, const int64_t* grp_off, const float* weights, int G,
+                                 int k, int fetch_k, int mode, double rrf_k, const uint64_t* masks_dev, int D,
+                                 int64_t mask_stride, const int32_t* mask_of_dev, double* fused_out_dev,
+                                 int64_t* rows_out_dev, uint32_t* members_out_dev, void* stream);
 int hr_index_size(hr_index* h, int64_t* n_out, int64_t* n_live_out);
 /* Shape of a handle (e.g. one returned by hr_index_load): dim, storage dtype, metric, devices. */
 int hr_index_info(hr_index* h, int* dim_out, int* dtype_out, int* metric_out, int* n_dev_out);

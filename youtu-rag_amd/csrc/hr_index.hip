@@ -1948,6 +1948,17 @@ static int validate_masks(hr_index* h, int B, int D, int64_t stride, const int32
     return HR_OK;
 }
 
+int index_validate_masks(hr_index* h, int B, int D, int64_t stride, const int32_t* mask_of_host) {
+    return validate_masks(h, B, D, stride, mask_of_host);
+}
+
+int index_search_masks_locked(hr_index* h, const float* q_dev, int B, int k, const uint64_t* masks_dev, int64_t stride,
+                              const int32_t* mask_of_dev, const int32_t* mask_of_host, float* s_out, int64_t* r_out,
+                              hipStream_t st) {
+    if (int rc = persist_close(h)) return rc;  // a running persistent FILTER leaves the CUs to this search
+    return search_masks_impl(h, q_dev, B, k, masks_dev, stride, mask_of_dev, mask_of_host, s_out, r_out, st);
+}
+
 // k > HR_MAX_K with per-query masks: the exhaustive pass per query with that query's bitmap, into host arrays
 static int masks_exact_all(hr_index* h, const float* q_dev, int B, int k, const uint64_t* masks_dev, int64_t stride,
                            const int32_t* mask_of_host, float* scores_out, int64_t* rows_out, hipStream_t st) {
@@ -2939,6 +2950,7 @@ extern "C" void hr_index_destroy(hr_index* h) {
     range_free(h);
     mmr_free(h);
     examples_free(h);
+    fused_free(h);
     (void)hipDeviceSynchronize();  // pipelined batches may still run on caller streams
     for (auto& g : h->sync_graphs)
         if (g.exec) (void)hipGraphExecDestroy(g.exec);

@@ -319,6 +319,11 @@ struct hr_index {
     DevBuf ex_list, ex_qin, ex_q, ex_mask, ex_s, ex_r, ex_cand, ex_out;  // lists, host base queries, built queries,
                                                                         // host mask, K' results / records, host results
     std::vector<uint8_t> ex_host;
+    // ---- fused multi-query search (hr_fuse.hip): every buffer allocated by the first call that needs it.  fu_list:
+    // one call's group offsets and weights as one block, packed in fu_host and copied once
+    DevBuf fu_list, fu_q, fu_masks, fu_of, fu_s, fu_r, fu_out;  // lists, host queries / bitmaps / mask_of, the members'
+                                                                // pools (scores, rows), host results
+    std::vector<uint8_t> fu_host;
 };
 
 // an internal stream of h: on h's CU mask when one is set (priority is then not available), else high priority or
@@ -397,6 +402,13 @@ int range_floors(const double* qerr, const float* min_score, int B, int Bp, doub
 void range_free(hr_index* h);  // hr_index_destroy's part
 void mmr_free(hr_index* h);  // hr_mmr.hip: hr_index_destroy's part
 void examples_free(hr_index* h);  // hr_examples.hip: hr_index_destroy's part
+void fused_free(hr_index* h);  // hr_fuse.hip: hr_index_destroy's part
+// hr_index_search_masks_device without the lock and the argument checks (hr_fuse.hip): mask_of_host holds the B
+// entries of mask_of_dev, already through index_validate_masks; 1 <= k <= HR_MAX_K (hr_index.hip)
+int index_validate_masks(hr_index* h, int B, int D, int64_t stride, const int32_t* mask_of_host);
+int index_search_masks_locked(hr_index* h, const float* q_dev, int B, int k, const uint64_t* masks_dev, int64_t stride,
+                              const int32_t* mask_of_dev, const int32_t* mask_of_host, float* s_out, int64_t* r_out,
+                              hipStream_t st);
 // the exhaustive exact pass of a k > HR_MAX_K search into device records out_dev[B][m] (hr_index.hip)
 int index_exact_dev(hr_index* h, const float* q_dev, int B, int m, const uint64_t* mask_dev, int64_t row_offset,
                     Cand* out_dev, hipStream_t st);

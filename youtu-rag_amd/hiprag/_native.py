@@ -24,6 +24,8 @@ HR_MAX_KC = 256
 HR_RANGE_MAX_HITS = 65536  # largest max_hits of search_range
 HR_EX_MAX = 32  # examples of one query of search_examples
 HR_EX_KEEP = 1  # search_examples flag: the examples stay candidates
+HR_FUSE_MAX_MEMBERS = 16  # lists of one group of search_fused / fuse_lists
+FUSE_MODES = {"rrf": 0, "max": 1}  # HR_FUSE_RRF, HR_FUSE_MAX
 HR_CREATE_NO_SHADOWS = 1
 HR_LEX_TERM_BITS = 22    # term id = crc32(token) % 2**22
 HR_LEX_MAX_QTERMS = 64
@@ -69,6 +71,7 @@ EXPORTS = [
     "hr_index_range_wave_tiles",
     "hr_index_build_queries", "hr_index_build_queries_device", "hr_index_search_examples",
     "hr_index_search_examples_device",
+    "hr_fuse_lists", "hr_index_search_fused", "hr_index_search_fused_device",
 ]
 
 _lib = None
@@ -234,6 +237,11 @@ def load_library(path: str | None = None):
             "hr_index_build_queries_device": [vp, vp, vp, vp, i32, vp, vp, vp],
             "hr_index_search_examples": [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp],
             "hr_index_search_examples_device": [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp],
+            "hr_fuse_lists": [i32, vp, vp, i32, vp, vp, i32, i32, i32, ctypes.c_double, vp, vp, vp, vp],
+            "hr_index_search_fused": [vp, vp, vp, vp, i32, i32, i32, i32, ctypes.c_double, vp, i32, i64, vp, vp, vp,
+                                      vp],
+            "hr_index_search_fused_device": [vp, vp, vp, vp, i32, i32, i32, i32, ctypes.c_double, vp, i32, i64, vp, vp,
+                                             vp, vp, vp],
         }
         for name, args in sig.items():
             if p != (path or LIB_PATH) and not hasattr(L, name):
@@ -686,6 +694,80 @@ class NativeIndex:
                                                         ctypes.c_void_p(scores_ptr), ctypes.c_void_p(rows_ptr),
                                                         ctypes.c_void_p(stream or None)))
 
+    # -- fused multi-query search (hr_fuse.hip): groups of queries, their exact lists fused on the device
+    def fuse_lists(self, rows_ptr: int, scores_ptr: int, P: int, groups, k: int, fused_ptr: int, rows_out_ptr: int,
+                   members_ptr: int = 0, mode: str = "rrf", rrf_k: float = 60.0, weights=None, stream: int = 0) -> None:
+        """fuse_lists() of the module on this index's device."""
+        fuse_lists(self.devices[0], rows_ptr, scores_ptr, P, groups, k, fused_ptr, rows_out_ptr, members_ptr, mode,
+                   rrf_k, weights, stream)
+
+    def _fused_args(self, groups, k, mode, weights):
+        off, w = _fuse_groups(groups, weights)
+        if int(k) <= 0 or int(k) > HR_MAX_K:  # (before the output arrays are sized by it)
+            raise ValueError(f"k must be in [1, {HR_MAX_K}]")
+        return off, w, _fuse_mode(mode)
+
+    def search_fused(self, q: np.ndarray, groups, k: int, fetch_k: int = 0, mode: str = "rrf", rrf_k: float = 60.0,
+                     weights=None, masks=None, mask_of=None) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Groups of queries answered as one fused list each (hr_index_search_fused).  ``groups``: the member count
+        of every group (the queries of ``q`` in order; 1 to 16 members each).  Every member is searched exactly for
+        ``fetch_k`` rows (0 = min(HR_MAX_K, max(4 k, 50)) for "rrf", k for "max"), all members in one scan, and the
+        lists of a group are fused on the device: ``mode="rrf"`` sums ``weights[i] / (rrf_k + rank)`` in float64 in
+        member order (``weights``: one fp32 value per query, default 1), ``mode="max"`` keeps the largest score.
+        ``masks`` / ``mask_of`` as search_masks: one row bitmap per member.  Returns ``(fused float64 (G, k), rows
+        int64 (G, k), members uint32 (G, k))``, fused score descending then row ascending, -inf / -1 / 0 after the
+        distinct rows; bit j of ``members`` says that member j of the group holds the row."""
+        q = np.ascontiguousarray(q, np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.shape[1] != self.dim:
+            raise ValueError(f"query dim {q.shape[1]} != index dim {self.dim}")
+        off, w, md = self._fused_args(groups, k, mode, weights)
+        Q, G = int(off[-1]), len(off) - 1
+        if q.shape[0] != Q:
+            raise ValueError(f"{q.shape[0]} queries for groups of {Q} members")
+        m, of, D, words = None, None, 0, 0
+        if mask_of is not None:
+            of = np.ascontiguousarray(np.asarray(mask_of, np.int32).reshape(-1))
+            if len(of) != Q:
+                raise ValueError(f"mask_of has {len(of)} entries for {Q} queries")
+            m = np.ascontiguousarray(masks, np.uint64) if masks is not None and len(masks) else np.zeros((0, 0), np.uint64)
+            if m.ndim == 1:
+                m = m[None, :]
+            D, words = int(m.shape[0]), int(m.shape[1]) if m.ndim == 2 else 0
+            if D:
+                n_rows = self.size()[0]
+                if words * 64 < n_rows:  # the library reads one bit per index row
+                    raise ValueError(f"row mask has {words} words, the index {n_rows} rows "
+                                     f"(needs {(n_rows + 63) // 64})")
+            elif (of >= 0).any():
+                raise ValueError("mask_of names a bitmap and there is none")
+        f = np.empty((G, int(k)), np.float64)
+        r = np.empty((G, int(k)), np.int64)
+        mem = np.empty((G, int(k)), np.uint32)
+        _check(self.lib.hr_index_search_fused(self._h, _ptr(q), _ptr(off), _ptr(w), G, int(k), int(fetch_k), md,
+                                              float(rrf_k), _ptr(m) if D else None, D, words,
+                                              _ptr(of) if D else None, _ptr(f), _ptr(r), _ptr(mem)))
+        return f, r, mem
+
+    def search_fused_device(self, q_ptr: int, groups, k: int, fused_ptr: int, rows_ptr: int, members_ptr: int = 0,
+                            fetch_k: int = 0, mode: str = "rrf", rrf_k: float = 60.0, weights=None, masks_ptr: int = 0,
+                            D: int = 0, mask_stride: int = 0, mask_of_ptr: int = 0, stream: int = 0) -> None:
+        """search_fused() with queries, bitmaps, mask_of and outputs in device memory (``groups`` and ``weights`` stay
+        host lists; ``members_ptr`` 0: no member bits); ordered after ``stream``, which is idle on return."""
+        off, w, md = self._fused_args(groups, k, mode, weights)
+        if D:
+            n_rows = self.size()[0]
+            if int(mask_stride) * 64 < n_rows:
+                raise ValueError(f"row mask has {int(mask_stride)} words, the index {n_rows} rows "
+                                 f"(needs {(n_rows + 63) // 64})")
+        _check(self.lib.hr_index_search_fused_device(self._h, ctypes.c_void_p(q_ptr), _ptr(off), _ptr(w), len(off) - 1,
+                                                     int(k), int(fetch_k), md, float(rrf_k),
+                                                     ctypes.c_void_p(masks_ptr or None), int(D), int(mask_stride),
+                                                     ctypes.c_void_p(mask_of_ptr or None), ctypes.c_void_p(fused_ptr),
+                                                     ctypes.c_void_p(rows_ptr), ctypes.c_void_p(members_ptr or None),
+                                                     ctypes.c_void_p(stream or None)))
+
     def search_device(self, q_ptr: int, B: int, k: int, scores_ptr: int, rows_ptr: int, mask_ptr: int = 0,
                       stream: int = 0) -> None:
         _check(self.lib.hr_index_search_device(self._h, ctypes.c_void_p(q_ptr), int(B), int(k),
@@ -1025,6 +1107,42 @@ def ivf_position_mask(ids_ptr: int, n_positions: int, row_mask_ptr: int, n_mask_
     _check(load_library().hr_ivf_position_mask(ctypes.c_void_p(ids_ptr or None), int(n_positions),
                                                ctypes.c_void_p(row_mask_ptr or None), int(n_mask_rows),
                                                ctypes.c_void_p(out_ptr or None), ctypes.c_void_p(stream or None)))
+
+
+def _fuse_groups(groups, weights):
+    """(offsets int64 (G + 1), weights fp32 (Q) or None) of a list of member counts."""
+    counts = np.asarray(list(groups), np.int64).reshape(-1)
+    if len(counts) == 0:
+        raise ValueError("a fused call needs at least one group")
+    if (counts < 1).any() or (counts > HR_FUSE_MAX_MEMBERS).any():
+        raise ValueError(f"a group takes 1 to {HR_FUSE_MAX_MEMBERS} members")
+    off = np.zeros(len(counts) + 1, np.int64)
+    np.cumsum(counts, out=off[1:])
+    w = None
+    if weights is not None:
+        w = np.ascontiguousarray(np.asarray(weights, np.float64).reshape(-1).astype(np.float32))
+        if len(w) != int(off[-1]):
+            raise ValueError(f"{len(w)} weights for {int(off[-1])} queries")
+    return off, w
+
+
+def _fuse_mode(mode) -> int:
+    if mode not in FUSE_MODES:
+        raise ValueError(f"mode must be one of {sorted(FUSE_MODES)} (got {mode!r})")
+    return FUSE_MODES[mode]
+
+
+def fuse_lists(device: int, rows_ptr: int, scores_ptr: int, P: int, groups, k: int, fused_ptr: int, rows_out_ptr: int,
+               members_ptr: int = 0, mode: str = "rrf", rrf_k: float = 60.0, weights=None, stream: int = 0) -> None:
+    """Ranked lists in device memory fused per group (hr_fuse_lists): ``rows_ptr`` / ``scores_ptr``: Q lists of P
+    slots (int64 rows, -1 = padding; fp32 scores), ``groups``: the member count of every group (1 to 16), outputs
+    G x k float64 fused scores, int64 rows and (``members_ptr`` != 0) uint32 member bits.  ``mode`` / ``rrf_k`` /
+    ``weights`` as NativeIndex.search_fused.  Ordered after ``stream``, which is idle on return."""
+    off, w = _fuse_groups(groups, weights)
+    _check(load_library().hr_fuse_lists(int(device), ctypes.c_void_p(rows_ptr), ctypes.c_void_p(scores_ptr), int(P),
+                                        _ptr(off), _ptr(w), len(off) - 1, int(k), _fuse_mode(mode), float(rrf_k),
+                                        ctypes.c_void_p(fused_ptr), ctypes.c_void_p(rows_out_ptr),
+                                        ctypes.c_void_p(members_ptr or None), ctypes.c_void_p(stream or None)))
 
 
 def topk_records(in_ptr: int, B: int, m: int, out_ptr: int, seg_stride: int = 0, seg_off_ptr: int = 0,

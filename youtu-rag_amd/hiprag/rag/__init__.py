@@ -9,13 +9,13 @@ from .config import (ChunkingConfig, EmbeddingConfig, KnowledgeBuilderConfig, Mo
 from .embeddings import EmbedderFactory, ServiceEmbedder, create_embedder
 from .rerankers import RerankerFactory, TorchRocmReranker
 from .retriever import BatchedVectorRetriever, HybridRetriever, VectorRetriever
-from .storage import HipVectorStore, RangeHits, VectorStoreFactory
+from .storage import FusedHits, HipVectorStore, RangeHits, VectorStoreFactory
 
 __all__ = [
     "BaseEmbedder", "BaseKnowledgeBuilder", "BaseReranker", "BaseRetriever", "BaseStorageMonitor", "BaseTextSplitter",
     "BaseVectorStore", "BuildStatus", "Chunk", "Document", "HealthStatus", "QueryRequest", "QueryResponse",
     "RetrievalResult", "RecursiveTextSplitter", "HierarchicalMarkdownSplitter", "ChunkingConfig", "EmbeddingConfig", "KnowledgeBuilderConfig",
     "MonitorConfig", "RAGConfig", "RetrieverConfig", "VectorStoreConfig", "EmbedderFactory", "ServiceEmbedder",
-    "create_embedder", "BatchedVectorRetriever", "HybridRetriever", "VectorRetriever", "HipVectorStore", "RangeHits",
+    "create_embedder", "BatchedVectorRetriever", "HybridRetriever", "VectorRetriever", "HipVectorStore", "RangeHits", "FusedHits",
     "VectorStoreFactory", "RerankerFactory", "TorchRocmReranker", "KnowledgeBuilder", "CourseSearcher",
 ]

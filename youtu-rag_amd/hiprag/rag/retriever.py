@@ -344,6 +344,35 @@ class VectorRetriever(BaseRetriever):
         results = self._to_results(hits, self.config.similarity_threshold)
         return await self._finish(query, results, top_k) if rerank else results[:top_k]
 
+    async def retrieve_fused(self, queries: list[str], top_k: int | None = None, *, fusion: str = "rrf",
+                             filters=None, rrf_k: float = 60, fetch_k: int | None = None, weights=None,
+                             similarity_threshold: float | None = None) -> list[RetrievalResult]:
+        """Several phrasings of ONE question -- rewrites, a HyDE answer, sub-questions -- answered as one list: one
+        ``embed_queries`` call over all of them and one fused search of the store (``search_fused``): every phrasing
+        searched exactly, the lists fused on the GPU.  ``fusion="rrf"``: reciprocal rank, ``sum of weight / (rrf_k +
+        rank)``; ``fusion="max"``: the best similarity any phrasing gives the chunk.  ``filters``: one where-clause, or
+        one per phrasing.  ``score`` is the fused score and ``rank`` counts from 1 (before the threshold).
+        ``similarity_threshold`` (default ``config.similarity_threshold``) applies to "max" scores only: an RRF score
+        is a sum of reciprocal ranks, not a similarity, and is never cut by it.  The optional reranker ranks against
+        the first phrasing; then ``[:top_k]``, as in retrieve()."""
+        search_fused = getattr(self.vector_store, "search_fused", None)
+        if search_fused is None:
+            raise NotImplementedError(f"{type(self.vector_store).__name__} has no fused search")
+        queries = list(queries)
+        if not queries:
+            return []
+        top_k = top_k or self.config.top_k
+        threshold = self.config.similarity_threshold if similarity_threshold is None else similarity_threshold
+        embed_many = getattr(self.embedder, "embed_queries", None)
+        qvs = await embed_many(queries) if embed_many else [await self.embedder.embed_query(q) for q in queries]
+        depth = top_k * 2 if self.reranker else top_k
+        if fetch_k is not None and fetch_k >= top_k:  # (the reranker's margin never asks for more than the pools hold)
+            depth = min(depth, int(fetch_k))
+        found = await search_fused(qvs, top_k=depth, filters=filters, fusion=fusion, rrf_k=rrf_k, fetch_k=fetch_k,
+                                   weights=weights)
+        results = self._to_results(found.hits, threshold if fusion == "max" else 0.0)
+        return await self._finish(queries[0], results, top_k)
+
     async def batch_retrieve(self, queries: list[str], top_k: int | None = None, **kwargs
                              ) -> list[list[RetrievalResult]]:
         return [await self.retrieve(query=q, top_k=top_k, **kwargs) for q in queries]

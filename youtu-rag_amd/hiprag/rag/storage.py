@@ -72,6 +72,14 @@ the named chunks never appear in their own answer (hr_index_search_examples; DES
 ``search_examples`` (several devices, IVF_FLAT) gets the same arithmetic composed on the host from ``get_rows`` and
 ``search``.  Calls do not go through the micro-batcher; the single-query form runs in a worker thread.
 
+Fused multi-query search (``search_fused_batch(query_groups, top_k, fusion="rrf" | "max")`` / ``await
+search_fused(query_embeddings)``): several query embeddings per question -- rewrites, a HyDE answer, sub-questions, each
+with its own where-clause if need be -- searched exactly in one scan and fused per question on the GPU, by reciprocal
+rank (``sum of weight / (rrf_k + rank)``) or by the best score (hr_index_search_fused).  Each group gets
+a ``FusedHits(hits, members)``: the (Chunk, fused score) pairs and per hit the bitmask of the group's queries that
+found it.  An index without a native ``search_fused`` (several devices, IVF_FLAT) gets the same arithmetic composed on
+the host from ``search``.  Calls do not go through the micro-batcher; the single-group form runs in a worker thread.
+
 ``index_type: "IVF_FLAT"`` (any letter case; single device, cosine / dot): the index is an ``IvfStoreIndex``
 (ivf_store.py) -- the same exact index plus an IVF replica that answers searches once ``ivf_train_rows`` live rows
 are stored (``index_params``: nlist, nprobe, ivf_train_rows = 64 nlist, ivf_seed).  It comes in through the
@@ -186,6 +194,49 @@ def search_examples_host(idx, examples, k: int, weights, q=None, mask=None, keep
         sel = np.nonzero(stay)[0][: int(k)]
         out_s[b, : len(sel)], out_r[b, : len(sel)] = s[b][sel], r[b][sel]
     return out_s, out_r
+
+
+def fuse_lists_host(scores, rows, groups, k: int, mode: str = "rrf", rrf_k: float = 60.0, weights=None):
+    """hr_fuse_lists restated in Python float (IEEE double) arithmetic: ``rows`` / ``scores`` are Q ranked lists of P
+    slots (row -1 = padding), ``groups`` the member count of every group.  "rrf": per distinct row 0.0, then per member
+    in member order ``fused = fused + float(fp32 weight) / (rrf_k + float(rank))``, ranks from 1; "max": the largest
+    fp32 score, NaN as -inf.  Ordered by fused descending, then row ascending; returns (fused float64 (G, k), rows
+    int64 (G, k), members uint32 (G, k)) with -inf / -1 / 0 after the distinct rows."""
+    rows, scores = np.asarray(rows, np.int64), np.asarray(scores, np.float32)
+    G, P = len(groups), rows.shape[1]
+    out_f = np.full((G, int(k)), -np.inf, np.float64)
+    out_r = np.full((G, int(k)), -1, np.int64)
+    out_m = np.zeros((G, int(k)), np.uint32)
+    rk, q0 = float(rrf_k), 0
+    for g, m in enumerate(groups):
+        acc: dict = {}  # row -> [fused, member bits]
+        for j in range(int(m)):
+            w = 1.0 if weights is None else float(np.float32(weights[q0 + j]))
+            r_l, s_l = rows[q0 + j].tolist(), scores[q0 + j].tolist()
+            for p in range(P):
+                r = r_l[p]
+                if r < 0:
+                    continue
+                if mode == "rrf":
+                    cur = acc.setdefault(r, [0.0, 0])
+                    cur[0] = cur[0] + w / (rk + float(p + 1))
+                else:
+                    cur = acc.setdefault(r, [-np.inf, 0])
+                    sc = s_l[p]
+                    if sc == sc and sc > cur[0]:  # (NaN counts as -inf)
+                        cur[0] = sc
+                cur[1] |= 1 << j
+        for t, (r, (f, bits)) in enumerate(sorted(acc.items(), key=lambda kv: (-kv[1][0], kv[0]))[: int(k)]):
+            out_f[g, t], out_r[g, t], out_m[g, t] = f, r, bits
+        q0 += int(m)
+    return out_f, out_r, out_m
+
+
+class FusedHits(NamedTuple):
+    """One group's answer to a fused search: its (Chunk, fused score) pairs, best first, and per hit the bitmask of
+    the group's members that found it (bit j: the j-th query of the group holds the chunk in its list)."""
+    hits: list
+    members: list
 
 
 class RangeHits(NamedTuple):
@@ -1521,6 +1572,132 @@ class HipVectorStore(BaseVectorStore):
         qe = None if query_embedding is None else np.asarray(query_embedding, np.float32).reshape(1, -1)
         prep = self._prep_similar([ids], neg, top_k, filters, qe, 1.0, 1.0)  # checked here: a bad request fails alone
         return self._assemble(prep, await asyncio.to_thread(self._run_similar, prep))[0]
+
+    # -- fused multi-query search (hr_index_search_fused): groups of queries, one fused list per group
+    def _prep_fused(self, query_groups, top_k: int, fusion: str, rrf_k, fetch_k, weights, filters):
+        """(q, member counts, top_k, pool depth, mode, rrf_k, flat fp32 weights or None, filters) of a fused search,
+        every limit of hr_index_search_fused checked: a bad request fails here, before any native call."""
+        if fusion not in _native.FUSE_MODES:
+            raise ValueError(f"fusion must be 'rrf' or 'max' (got {fusion!r})")
+        groups = [np.asarray(g, dtype=np.float32) for g in query_groups]
+        groups = [g[None, :] if g.ndim == 1 else g for g in groups]
+        counts = [int(g.shape[0]) for g in groups]
+        if any(m < 1 or m > _native.HR_FUSE_MAX_MEMBERS or g.ndim != 2 for m, g in zip(counts, groups)):
+            raise ValueError(f"a group takes 1 to {_native.HR_FUSE_MAX_MEMBERS} query embeddings")
+        dim = self.dim if self.dim is not None else (groups[0].shape[1] if groups else 0)
+        if any(g.shape[1] != dim for g in groups):
+            raise ValueError(f"query dim != collection dim {dim}")
+        q = np.concatenate(groups) if groups else np.zeros((0, dim or 1), np.float32)
+        k, top = int(top_k), _native.HR_MAX_K
+        if k > top:
+            raise ValueError(f"a fused search returns at most {top} hits (top_k = {top_k})")
+        rk = float(rrf_k)
+        if not (np.isfinite(rk) and rk >= 0.0):
+            raise ValueError(f"rrf_k must be finite and not negative (got {rrf_k})")
+        pool = (max(k, 1) if fusion == "max" else min(top, max(4 * k, 50))) if fetch_k is None else int(fetch_k)
+        if pool < max(k, 1) or pool > top:
+            raise ValueError(f"fetch_k must be in [top_k, {top}] (got {fetch_k}, top_k = {top_k})")
+        w = None
+        if weights is not None:
+            if fusion == "max":
+                raise ValueError("max fusion takes no weights")
+            weights = [list(np.atleast_1d(np.asarray(ws, np.float64))) for ws in weights]
+            if [len(ws) for ws in weights] != counts:
+                raise ValueError("weights must have the shape of query_groups")
+            w = np.asarray([v for ws in weights for v in ws], np.float64).astype(np.float32)
+            if not np.isfinite(w).all():
+                raise ValueError("weights must be finite")
+        if isinstance(filters, (list, tuple)):  # one where-clause (or None) per member, in flattened order
+            filters = list(filters)
+            if len(filters) != len(q):
+                raise ValueError(f"{len(filters)} filters for {len(q)} queries")
+            if len({_filter_key(f) for f in filters}) == 1:
+                filters = filters[0] or None
+            elif not self.mixed_filters:
+                raise ValueError("one filter per member needs index_params.mixed_filters = true")
+        return q, counts, k, pool, fusion, rk, w, filters
+
+    def _run_fused(self, prep):
+        """The fused search under the store lock, as _run_search: ((fused, rows, members) or None, tables).  Natively
+        where the index can (a single-device exact index), else composed on the host from its plain search -- one per
+        distinct filter -- and fuse_lists_host: the same results."""
+        q, counts, k, pool, mode, rk, w, filters = prep
+        with self._lock:  # ordered against mutations
+            tables = (self._records, self._metas, self._epoch)
+            idx, n_live = self._index, self.count_sync()
+            if idx is None or n_live == 0 or k <= 0 or not counts:
+                return None, tables
+            native = hasattr(idx, "search_fused") and not self.ivf and len(getattr(idx, "devices", (0,))) == 1
+            if isinstance(filters, list):
+                clauses, clause_of, bitmaps = self._distinct_filters(filters)
+                if native:
+                    masks, mask_of = self._stack_bitmaps(bitmaps, clause_of)
+                    self.mixed_launches += 1
+                    return idx.search_fused(q, counts, k, pool, mode, rk, w, masks, mask_of), tables
+            elif native:
+                bm = self.filter_bitmap(filters)
+                masks, mask_of = (None, None) if bm is None else (bm, np.zeros(len(q), np.int32))
+                return idx.search_fused(q, counts, k, pool, mode, rk, w, masks, mask_of), tables
+            depth = min(pool, n_live)  # (an index's plain search may refuse more rows than it has)
+            scores = np.full((len(q), pool), -np.inf, np.float32)
+            rows = np.full((len(q), pool), -1, np.int64)
+            if isinstance(filters, list):
+                for c in range(len(clauses)):
+                    sel = np.nonzero(clause_of == c)[0]
+                    scores[sel, :depth], rows[sel, :depth] = idx.search(q[sel], depth, bitmaps[c])
+                    self.grouped_launches += 1
+            else:
+                scores[:, :depth], rows[:, :depth] = idx.search(q, depth, self.filter_bitmap(filters))
+            return fuse_lists_host(scores, rows, counts, k, mode, rk, w), tables
+
+    def _assemble_fused(self, n_groups: int, ran) -> list[FusedHits]:
+        raw, (recs, metas, epoch) = ran
+        if raw is None or epoch != self._epoch:
+            return [FusedHits([], []) for _ in range(n_groups)]
+        fused, rows, members = raw
+        valid = (rows >= 0) & (rows < min(len(recs), len(metas)))
+        hit_rows = rows[valid]
+        rec_l, meta_l = recs.a[hit_rows].tolist(), metas.a[hit_rows].tolist()
+        score_l, mem_l, per_g = fused[valid].tolist(), members[valid].tolist(), valid.sum(axis=1).tolist()
+        out, i = [], 0
+        for cnt in per_g:
+            hits, mem = [], []
+            for j in range(i, i + cnt):
+                r = rec_l[j]
+                if r is None:  # deleted since the search ran
+                    continue
+                m = meta_l[j]
+                hits.append((Chunk(r[0], m.get("document_id", ""), r[2], m.get("chunk_index", 0), dict(m), None),
+                             score_l[j]))
+                mem.append(int(mem_l[j]))
+            out.append(FusedHits(hits, mem))
+            i += cnt
+        return out
+
+    def search_fused_batch(self, query_groups, top_k: int = 5, *, fusion: str = "rrf", rrf_k: float = 60,
+                           fetch_k: int | None = None, weights=None, filters=None) -> list[FusedHits]:
+        """Several queries per question, one fused list per question: ``query_groups`` is a list of groups, each 1 to
+        16 query embeddings (rewrites, HyDE answers, sub-questions of one question).  Every member is searched exactly
+        for ``fetch_k`` chunks -- all members of all groups in one scan -- and each group's lists are fused on the GPU.
+        ``fusion="rrf"``: reciprocal rank, ``sum of weight / (rrf_k + rank)`` over the members holding the chunk, in
+        float64 in member order (``weights``: the shape of ``query_groups``, default 1; ``fetch_k`` default
+        ``min(128, max(4 top_k, 50))``; the score is a function of the rank window, not a similarity).
+        ``fusion="max"``: the largest similarity any member gives the chunk (what merging searches by score does;
+        ``fetch_k`` default ``top_k``; no weights).  Ordered by fused score descending, then row ascending.
+        ``filters``: one where-clause for everything, or a list with one (or None) per member in flattened order (needs
+        ``index_params.mixed_filters``).  Per group a FusedHits: the (Chunk, fused score) pairs and, per hit, the
+        bitmask of the members that found it.  An index without the native call (IVF_FLAT, multi-device) is composed on
+        the host from its plain search, with the same results wherever that search is exact."""
+        prep = self._prep_fused(query_groups, top_k, fusion, rrf_k, fetch_k, weights, filters)
+        return self._assemble_fused(len(prep[1]), self._run_fused(prep))
+
+    async def search_fused(self, query_embeddings, top_k: int = 5, filters=None, *, fusion: str = "rrf",
+                           rrf_k: float = 60, fetch_k: int | None = None, weights=None) -> FusedHits:
+        """One group -- the query embeddings of one question -- off the event loop; keywords as search_fused_batch
+        (``weights``: one per embedding; ``filters``: one where-clause or one per embedding)."""
+        prep = self._prep_fused([query_embeddings], top_k, fusion, rrf_k, fetch_k,
+                                None if weights is None else [weights], filters)  # a bad request fails alone
+        return self._assemble_fused(1, await asyncio.to_thread(self._run_fused, prep))[0]
 
     def get_by_id_sync(self, chunk_id: str) -> Chunk | None:
         with self._lock:
