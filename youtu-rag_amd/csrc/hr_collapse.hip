@@ -158,21 +158,6 @@ __global__ void k_collapse_take(const Cand* __restrict__ top, int k, float* __re
     r_out[i] = e.row >= 0 ? e.row : -1;
 }
 
-__global__ void k_collapse_pad(float* __restrict__ s_out, int64_t* __restrict__ r_out, int64_t n) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    s_out[i] = -__builtin_inff();
-    r_out[i] = -1;
-}
-
-size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-int pad_results(float* s_out, int64_t* r_out, int64_t n, hipStream_t st) {
-    hipLaunchKernelGGL(k_collapse_pad, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, s_out, r_out, n);
-    HIP_TRY(hipGetLastError());
-    return HR_OK;
-}
-
 // one incomplete query through the all-rows pass; qv: its canonical fp32 query (dpad floats), qn2 = |q|^2
 int collapse_all_rows(hr_index* h, const float* qv, double qn2, const uint64_t* mask_dev, int k, float* s_out,
                       int64_t* r_out, hipStream_t st) {
@@ -224,15 +209,15 @@ int collapsed_impl(hr_index* h, const float* q_dev, int B, int k, int probe, con
     if (timed)
         for (auto& e : h->col_ev)
             if (!e) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(h->col_s.ensure((size_t)B * P * 4));
-    HIP_TRY(h->col_r.ensure((size_t)B * P * 8));
+    HIP_TRY(h->pool_s.ensure((size_t)B * P * 4));
+    HIP_TRY(h->pool_r.ensure((size_t)B * P * 8));
     HIP_TRY(h->col_flag.ensure((size_t)B * 4));
     if (timed) HIP_TRY(hipEventRecord(h->col_ev[0], st));
-    if (int rc = index_search_locked(h, q_dev, B, P, mask_dev, h->col_s.as<float>(), h->col_r.as<int64_t>(), st))
+    if (int rc = index_search_locked(h, q_dev, B, P, mask_dev, h->pool_s.as<float>(), h->pool_r.as<int64_t>(), st))
         return rc;
     if (timed) HIP_TRY(hipEventRecord(h->col_ev[1], st));
-    hipLaunchKernelGGL(k_collapse_prefix, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, h->col_s.as<float>(),
-                       h->col_r.as<int64_t>(), B, P, k, h->groups, h->groups_cap, s_out, r_out,
+    hipLaunchKernelGGL(k_collapse_prefix, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, h->pool_s.as<float>(),
+                       h->pool_r.as<int64_t>(), B, P, k, h->groups, h->groups_cap, s_out, r_out,
                        h->col_flag.as<int32_t>());
     HIP_TRY(hipGetLastError());
     if (timed) HIP_TRY(hipEventRecord(h->col_ev[2], st));
@@ -277,9 +262,7 @@ void collapse_free(hr_index* h) {
     if (h->groups) (void)hipFree(h->groups);
     h->groups = nullptr;
     h->groups_cap = 0;
-    for (DevBuf* b : {&h->col_q, &h->col_mask, &h->col_s, &h->col_r, &h->col_flag, &h->col_out, &h->col_keys, &h->col_g,
-                      &h->col_top})
-        b->release();
+    for (DevBuf* b : {&h->col_flag, &h->col_keys, &h->col_g, &h->col_top}) b->release();
     for (auto& e : h->col_ev) {
         if (e) (void)hipEventDestroy(e);
         e = nullptr;
@@ -342,22 +325,14 @@ extern "C" int hr_index_search_collapsed(hr_index* h, const float* q, int B, int
     if (B <= 0) return set_err(HR_E_INVALID, "B must be positive");
     if (k <= 0 || k > HR_MAX_K) return set_err(HR_E_INVALID, "k must be in [1, HR_MAX_K]");
     hipStream_t st = h->stream;
-    const size_t words = (size_t)((h->n + 63) / 64);
-    const size_t off_r = up256((size_t)B * k * 4);
-    HIP_TRY(h->col_q.ensure((size_t)B * h->dim * 4));
-    HIP_TRY(h->col_out.ensure(off_r + (size_t)B * k * 8));
+    OutSeg out[2] = {{scores_out, (size_t)B * k * 4}, {rows_out, (size_t)B * k * 8}};
+    float* q_dev = nullptr;
     uint64_t* m_dev = nullptr;
-    if (row_mask && words) {
-        HIP_TRY(h->col_mask.ensure(words * 8));
-        m_dev = h->col_mask.as<uint64_t>();
-        HIP_TRY(hipMemcpyAsync(m_dev, row_mask, words * 8, hipMemcpyHostToDevice, st));
-    }
-    HIP_TRY(hipMemcpyAsync(h->col_q.p, q, (size_t)B * h->dim * 4, hipMemcpyHostToDevice, st));
-    float* s_dev = h->col_out.as<float>();
-    int64_t* r_dev = (int64_t*)(h->col_out.as<uint8_t>() + off_r);
-    if (int rc = collapsed_impl(h, h->col_q.as<float>(), B, k, probe, m_dev, s_dev, r_dev, st)) return rc;
-    HIP_TRY(hipMemcpyAsync(scores_out, s_dev, (size_t)B * k * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(rows_out, r_dev, (size_t)B * k * 8, hipMemcpyDeviceToHost, st));
+    if (int rc = stage_out(h, out)) return rc;
+    if (int rc = stage_mask(h, row_mask, st, &m_dev)) return rc;
+    if (int rc = stage_queries(h, q, B, st, &q_dev)) return rc;
+    if (int rc = collapsed_impl(h, q_dev, B, k, probe, m_dev, out[0].as<float>(), out[1].as<int64_t>(), st)) return rc;
+    if (int rc = stage_download(out, st)) return rc;
     HIP_TRY(hipStreamSynchronize(st));
     return HR_OK;
 }

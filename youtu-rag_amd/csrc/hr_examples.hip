@@ -122,8 +122,6 @@ __global__ __launch_bounds__(256) void k_drop_examples(const float* __restrict__
     }
 }
 
-size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct Lists {  // one call's example lists on the device (h->ex_list)
     const int64_t* off = nullptr;
     const int64_t* rows = nullptr;
@@ -196,7 +194,7 @@ int launch_drop(const float* s_in, const int64_t* r_in, const Cand* c_in, int Kp
 int examples_impl(hr_index* h, const Lists& L, const float* q_dev, int B, int k, int flags, const uint64_t* mask_dev,
                   float* s_out, int64_t* r_out, hipStream_t st) {
     if (h->n_live == 0) {  // empty index (only base vectors pass the checks): padding, as hr_index_search
-        if (int rc = launch_drop(nullptr, nullptr, nullptr, 0, k, B, nullptr, s_out, r_out, st)) return rc;
+        if (int rc = pad_results(s_out, r_out, (int64_t)B * k, st)) return rc;
         HIP_TRY(hipStreamSynchronize(st));
         return HR_OK;
     }
@@ -215,11 +213,11 @@ int examples_impl(hr_index* h, const Lists& L, const float* q_dev, int B, int k,
         return HR_OK;
     }
     if (M == 0) return index_search_locked(h, built, B, k, mask_dev, s_out, r_out, st);  // nothing to drop
-    HIP_TRY(h->ex_s.ensure((size_t)B * Kp * 4));
-    HIP_TRY(h->ex_r.ensure((size_t)B * Kp * 8));
-    if (int rc = index_search_locked(h, built, B, Kp, mask_dev, h->ex_s.as<float>(), h->ex_r.as<int64_t>(), st))
+    HIP_TRY(h->pool_s.ensure((size_t)B * Kp * 4));
+    HIP_TRY(h->pool_r.ensure((size_t)B * Kp * 8));
+    if (int rc = index_search_locked(h, built, B, Kp, mask_dev, h->pool_s.as<float>(), h->pool_r.as<int64_t>(), st))
         return rc;
-    if (int rc = launch_drop(h->ex_s.as<float>(), h->ex_r.as<int64_t>(), nullptr, Kp, k, B, &L, s_out, r_out, st))
+    if (int rc = launch_drop(h->pool_s.as<float>(), h->pool_r.as<int64_t>(), nullptr, Kp, k, B, &L, s_out, r_out, st))
         return rc;
     HIP_TRY(hipStreamSynchronize(st));
     return HR_OK;
@@ -234,8 +232,7 @@ int check_search(int k, int flags) {
 }  // namespace
 
 void examples_free(hr_index* h) {
-    for (DevBuf* b : {&h->ex_list, &h->ex_qin, &h->ex_q, &h->ex_mask, &h->ex_s, &h->ex_r, &h->ex_cand, &h->ex_out})
-        b->release();
+    for (DevBuf* b : {&h->ex_list, &h->ex_q, &h->ex_cand}) b->release();
 }
 
 extern "C" int hr_index_build_queries_device(hr_index* h, const int64_t* ex_rows, const float* ex_weights,
@@ -264,11 +261,10 @@ extern "C" int hr_index_build_queries(hr_index* h, const int64_t* ex_rows, const
     Lists L;
     if (int rc = stage_lists(h, ex_rows, ex_weights, ex_off, B, st, &L)) return rc;
     HIP_TRY(h->ex_q.ensure(qb));
-    if (q) {
-        HIP_TRY(h->ex_qin.ensure(qb));
-        HIP_TRY(hipMemcpyAsync(h->ex_qin.p, q, qb, hipMemcpyHostToDevice, st));
-    }
-    if (int rc = launch_build(h, L, B, q ? h->ex_qin.as<float>() : nullptr, h->ex_q.as<float>(), st)) return rc;
+    float* q_dev = nullptr;
+    if (q)
+        if (int rc = stage_queries(h, q, B, st, &q_dev)) return rc;
+    if (int rc = launch_build(h, L, B, q_dev, h->ex_q.as<float>(), st)) return rc;
     HIP_TRY(hipMemcpyAsync(q_out, h->ex_q.p, qb, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return HR_OK;
@@ -300,25 +296,16 @@ extern "C" int hr_index_search_examples(hr_index* h, const float* q, const int64
     hipStream_t st = h->stream;
     Lists L;
     if (int rc = stage_lists(h, ex_rows, ex_weights, ex_off, B, st, &L)) return rc;
-    const size_t words = (size_t)((h->n + 63) / 64), nk = (size_t)B * k, off_r = up256(nk * 4);
-    HIP_TRY(h->ex_out.ensure(off_r + nk * 8));
+    OutSeg out[2] = {{scores_out, (size_t)B * k * 4}, {rows_out, (size_t)B * k * 8}};
     float* q_dev = nullptr;
-    if (q) {
-        HIP_TRY(h->ex_qin.ensure((size_t)B * h->dim * 4));
-        q_dev = h->ex_qin.as<float>();
-        HIP_TRY(hipMemcpyAsync(q_dev, q, (size_t)B * h->dim * 4, hipMemcpyHostToDevice, st));
-    }
     uint64_t* m_dev = nullptr;
-    if (row_mask && words) {
-        HIP_TRY(h->ex_mask.ensure(words * 8));
-        m_dev = h->ex_mask.as<uint64_t>();
-        HIP_TRY(hipMemcpyAsync(m_dev, row_mask, words * 8, hipMemcpyHostToDevice, st));
-    }
-    float* s_dev = h->ex_out.as<float>();
-    int64_t* r_dev = (int64_t*)(h->ex_out.as<uint8_t>() + off_r);
-    if (int rc = examples_impl(h, L, q_dev, B, k, flags, m_dev, s_dev, r_dev, st)) return rc;
-    HIP_TRY(hipMemcpyAsync(scores_out, s_dev, nk * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(rows_out, r_dev, nk * 8, hipMemcpyDeviceToHost, st));
+    if (int rc = stage_out(h, out)) return rc;
+    if (q)
+        if (int rc = stage_queries(h, q, B, st, &q_dev)) return rc;
+    if (int rc = stage_mask(h, row_mask, st, &m_dev)) return rc;
+    if (int rc = examples_impl(h, L, q_dev, B, k, flags, m_dev, out[0].as<float>(), out[1].as<int64_t>(), st))
+        return rc;
+    if (int rc = stage_download(out, st)) return rc;
     HIP_TRY(hipStreamSynchronize(st));
     return HR_OK;
 }

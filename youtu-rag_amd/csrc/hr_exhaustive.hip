@@ -15,8 +15,7 @@
 #include <rocprim/device/device_select.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
 
-#include "../../include/hiprag.h"
-#include "hr_common.hpp"
+#include "hr_internal.hpp"
 
 namespace {
 
@@ -108,8 +107,7 @@ size_t exhaustive_scratch_bytes(int64_t n) {
     if (rocprim::radix_sort_pairs_desc(nullptr, tmp, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr,
                                        (uint32_t*)nullptr, (size_t)n, 0, 64) != hipSuccess)
         tmp = 0;  // the sort call below then reports the error
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    return up(8 * (size_t)n) * 2 + up(4 * (size_t)n) * 2 + up(tmp);
+    return up256(8 * (size_t)n) * 2 + up256(4 * (size_t)n) * 2 + up256(tmp);
 }
 
 // exact top-m (score desc, row asc) of query qv over rows [0, n) into out[0..m); empty slots -inf / -1;
@@ -124,13 +122,13 @@ int exhaustive_topm(const uint8_t* rows, int dtype, int S, int dpad, const float
                            (const uint32_t*)nullptr, (int64_t)0, m, row_offset, sG, ss, out);
         return hipGetLastError() == hipSuccess ? HR_OK : HR_E_HIP;
     }
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t k8 = up256(8 * (size_t)n), v4 = up256(4 * (size_t)n);
     uint8_t* p = (uint8_t*)scratch;
     uint64_t* k_in = (uint64_t*)p;
-    uint64_t* k_out = (uint64_t*)(p + up(8 * (size_t)n));
-    uint32_t* v_in = (uint32_t*)(p + 2 * up(8 * (size_t)n));
-    uint32_t* v_out = (uint32_t*)(p + 2 * up(8 * (size_t)n) + up(4 * (size_t)n));
-    uint8_t* tmp = p + 2 * up(8 * (size_t)n) + 2 * up(4 * (size_t)n);
+    uint64_t* k_out = (uint64_t*)(p + k8);
+    uint32_t* v_in = (uint32_t*)(p + 2 * k8);
+    uint32_t* v_out = (uint32_t*)(p + 2 * k8 + v4);
+    uint8_t* tmp = p + 2 * k8 + 2 * v4;
     if (scratch_bytes < exhaustive_scratch_bytes(n)) return HR_E_INVALID;
     size_t tmp_bytes = scratch_bytes - (size_t)(tmp - p);
     if (int rc = exact_all_keys(rows, dtype, S, dpad, qv, metric, qn2, live, mask, n, k_in, v_in, st)) return rc;
@@ -185,11 +183,18 @@ __global__ void k_pad_results(float* __restrict__ s_out, int64_t* __restrict__ r
     r_out[i] = -1;
 }
 
+int pad_results(float* s_out, int64_t* r_out, int64_t n, hipStream_t st) {
+    for (int64_t o = 0; o < n; o += (int64_t)1 << 30) {  // (the range search pads up to B * HR_RANGE_MAX_HITS slots)
+        const int64_t c = std::min<int64_t>(n - o, (int64_t)1 << 30);
+        hipLaunchKernelGGL(k_pad_results, dim3((unsigned)((c + 255) / 256)), dim3(256), 0, st, s_out + o, r_out + o, c);
+    }
+    HIP_TRY(hipGetLastError());
+    return HR_OK;
+}
+
 int launch_merge_sorted(const Cand* cand, int64_t cstride, int G, int B, int m, int k, float* s_out, int64_t* r_out,
                         hipStream_t st) {
-    const int64_t nk = (int64_t)B * k;
-    hipLaunchKernelGGL(k_pad_results, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, st, s_out, r_out, nk);
-    if (hipGetLastError() != hipSuccess) return HR_E_HIP;
+    if (pad_results(s_out, r_out, (int64_t)B * k, st)) return HR_E_HIP;
     const int64_t per_q = (int64_t)G * m;
     hipLaunchKernelGGL(k_merge_sorted, dim3((unsigned)((per_q + 255) / 256), (unsigned)B), dim3(256), 0, st,
                        (const uint8_t*)cand, cstride, G, B, m, k, s_out, r_out);

@@ -127,8 +127,6 @@ __global__ void k_fuse_pad(double* __restrict__ fused_out, int64_t* __restrict__
     if (members_out) members_out[i] = 0u;
 }
 
-size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // everything hr_fuse_lists refuses, before any device call
 int check_fuse(int P, const int64_t* grp_off, const float* weights, int G, int k, int mode, double rrf_k) {
     if (!grp_off) return set_err(HR_E_INVALID, "null argument");
@@ -208,10 +206,10 @@ int fused_impl(hr_index* h, const float* q_dev, const int64_t* grp_off, const fl
         HIP_TRY(hipStreamSynchronize(st));
         return HR_OK;
     }
-    HIP_TRY(h->fu_s.ensure((size_t)Q * P * 4));
-    HIP_TRY(h->fu_r.ensure((size_t)Q * P * 8));
-    float* ps = h->fu_s.as<float>();
-    int64_t* pr = h->fu_r.as<int64_t>();
+    HIP_TRY(h->pool_s.ensure((size_t)Q * P * 4));
+    HIP_TRY(h->pool_r.ensure((size_t)Q * P * 8));
+    float* ps = h->pool_s.as<float>();
+    int64_t* pr = h->pool_r.as<int64_t>();
     bool same = true;  // every member names the same bitmap (or none): the single-mask search, identical by contract
     for (int i = 1; of && i < Q; ++i) same = same && of[i] == of[0];
     if (!of || same) {
@@ -234,7 +232,7 @@ std::vector<uint8_t> g_fuse_host;
 }  // namespace
 
 void fused_free(hr_index* h) {
-    for (DevBuf* b : {&h->fu_list, &h->fu_q, &h->fu_masks, &h->fu_of, &h->fu_s, &h->fu_r, &h->fu_out}) b->release();
+    h->fu_list.release();
 }
 
 extern "C" int hr_fuse_lists(int device, const int64_t* rows_dev, const float* scores_dev, int P, const int64_t* grp_off,
@@ -293,29 +291,21 @@ extern "C" int hr_index_search_fused(hr_index* h, const float* q, const int64_t*
         if (int rc = index_validate_masks(h, Q, D, mask_stride, mask_of)) return rc;
     if (int rc = set_device(h)) return rc;
     hipStream_t st = h->stream;
-    const size_t nk = (size_t)G * k, off_r = up256(nk * 8), off_m = off_r + up256(nk * 8);
-    HIP_TRY(h->fu_q.ensure((size_t)Q * h->dim * 4));
-    HIP_TRY(h->fu_out.ensure(off_m + nk * 4));
-    HIP_TRY(hipMemcpyAsync(h->fu_q.p, q, (size_t)Q * h->dim * 4, hipMemcpyHostToDevice, st));
-    // only the words that cover the index go up: D bitmaps, words64 apart on the device
+    const size_t nk = (size_t)G * k;
+    OutSeg out[3] = {{fused_out, nk * 8}, {rows_out, nk * 8}, {members_out, nk * 4}};
+    float* q_dev = nullptr;
+    uint64_t* masks_dev = nullptr;
+    int32_t* of_dev = nullptr;
+    if (int rc = stage_out(h, out)) return rc;
+    if (int rc = stage_queries(h, q, Q, st, &q_dev)) return rc;
     const int64_t words64 = (h->n + 63) / 64;
-    const bool masked = D > 0 && words64 > 0;
-    if (masked) {
-        HIP_TRY(h->fu_masks.ensure((size_t)D * words64 * 8));
-        HIP_TRY(h->fu_of.ensure((size_t)Q * 4));
-        HIP_TRY(hipMemcpy2DAsync(h->fu_masks.p, (size_t)words64 * 8, masks, (size_t)mask_stride * 8, (size_t)words64 * 8,
-                                 (size_t)D, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(h->fu_of.p, mask_of, (size_t)Q * 4, hipMemcpyHostToDevice, st));
-    }
-    double* f_dev = h->fu_out.as<double>();
-    int64_t* r_dev = (int64_t*)(h->fu_out.as<uint8_t>() + off_r);
-    uint32_t* m_dev = members_out ? (uint32_t*)(h->fu_out.as<uint8_t>() + off_m) : nullptr;
-    if (int rc = fused_impl(h, h->fu_q.as<float>(), grp_off, weights, G, k, P, mode, rrf_k, h->fu_masks.as<uint64_t>(),
-                            words64, h->fu_of.as<int32_t>(), masked ? mask_of : nullptr, f_dev, r_dev, m_dev, st))
+    const bool masked = D > 0 && words64 > 0;  // else: the plain search, and no pointer of an earlier call's masks
+    if (masked)
+        if (int rc = stage_masks(h, masks, D, mask_stride, mask_of, Q, st, &masks_dev, &of_dev)) return rc;
+    if (int rc = fused_impl(h, q_dev, grp_off, weights, G, k, P, mode, rrf_k, masks_dev, words64, of_dev,
+                            masked ? mask_of : nullptr, out[0].as<double>(), out[1].as<int64_t>(), out[2].as<uint32_t>(), st))
         return rc;
-    HIP_TRY(hipMemcpyAsync(fused_out, f_dev, nk * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(rows_out, r_dev, nk * 8, hipMemcpyDeviceToHost, st));
-    if (members_out) HIP_TRY(hipMemcpyAsync(members_out, m_dev, nk * 4, hipMemcpyDeviceToHost, st));
+    if (int rc = stage_download(out, st)) return rc;
     HIP_TRY(hipStreamSynchronize(st));
     return HR_OK;
 }

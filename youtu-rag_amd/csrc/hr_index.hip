@@ -268,7 +268,7 @@ int index_update_row_norms(hr_index* h, int64_t r0, int64_t n) {
     });
 }
 
-// SRC: where the fp32 rows come from (host memory staged through h->stage, the generator, or device memory).
+// SRC: where the fp32 rows come from (host memory staged through h->hs.out, the generator, or device memory).
 enum { ADD_HOST = 0, ADD_SYNTH = 1, ADD_DEVICE = 2 };
 
 // ADD_SYNTH: local row L gets generator row gen_base + stripe_row(L) (hr_common.hpp)
@@ -283,10 +283,10 @@ static int add_impl(hr_index* h, const float* rows, uint64_t seed, int64_t gen_b
         const int64_t m = std::min(chunk, n - off);
         const float* src = nullptr;
         if (SRC == ADD_HOST) {
-            HIP_TRY(h->stage.ensure((size_t)m * h->dim * 4));
-            HIP_TRY(hipMemcpyAsync(h->stage.p, rows + off * h->dim, (size_t)m * h->dim * 4, hipMemcpyHostToDevice,
+            HIP_TRY(h->hs.out.ensure((size_t)m * h->dim * 4));
+            HIP_TRY(hipMemcpyAsync(h->hs.out.p, rows + off * h->dim, (size_t)m * h->dim * 4, hipMemcpyHostToDevice,
                                    h->stream));
-            src = h->stage.as<float>();
+            src = h->hs.out.as<float>();
         } else if (SRC == ADD_DEVICE) {
             src = rows + off * h->dim;
         }
@@ -2025,30 +2025,20 @@ extern "C" int hr_index_search_masks(hr_index* h, const float* q, int B, int k, 
         return HR_OK;
     }
     hipStream_t st = h->stream;
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t kk = (size_t)std::min(k, HR_MAX_K);  // (k > HR_MAX_K writes the host arrays directly)
-    const size_t off_r = up((size_t)B * kk * 4);
-    HIP_TRY(h->q_in.ensure((size_t)B * h->dim * 4));
-    HIP_TRY(h->stage.ensure(off_r + up((size_t)B * kk * 8)));
-    HIP_TRY(h->qm_of.ensure((size_t)B * 4));
-    // only the words that cover the index go up: D bitmaps, words64 apart on the device
+    OutSeg out[2] = {{scores_out, (size_t)B * kk * 4}, {rows_out, (size_t)B * kk * 8}};
     const int64_t words64 = (h->n + 63) / 64;
-    HIP_TRY(h->qm_masks.ensure(std::max<size_t>(8, (size_t)D * words64 * 8)));
-    float* s_dev = h->stage.as<float>();
-    int64_t* r_dev = (int64_t*)(h->stage.as<uint8_t>() + off_r);
-    HIP_TRY(hipMemcpyAsync(h->q_in.p, q, (size_t)B * h->dim * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(h->qm_of.p, mask_of, (size_t)B * 4, hipMemcpyHostToDevice, st));
-    if (D > 0)
-        HIP_TRY(hipMemcpy2DAsync(h->qm_masks.p, (size_t)words64 * 8, masks, (size_t)mask_stride * 8, (size_t)words64 * 8,
-                                 (size_t)D, hipMemcpyHostToDevice, st));
-    if (k > HR_MAX_K)
-        return masks_exact_all(h, h->q_in.as<float>(), B, k, h->qm_masks.as<uint64_t>(), words64, mask_of, scores_out,
-                               rows_out, st);
-    if (int rc = search_masks_impl(h, h->q_in.as<float>(), B, k, h->qm_masks.as<uint64_t>(), words64, h->qm_of.as<int32_t>(),
-                                   mask_of, s_dev, r_dev, st))
+    float* q_dev = nullptr;
+    uint64_t* masks_dev = nullptr;
+    int32_t* of_dev = nullptr;
+    if (int rc = stage_out(h, out)) return rc;
+    if (int rc = stage_queries(h, q, B, st, &q_dev)) return rc;
+    if (int rc = stage_masks(h, masks, D, mask_stride, mask_of, B, st, &masks_dev, &of_dev)) return rc;
+    if (k > HR_MAX_K) return masks_exact_all(h, q_dev, B, k, masks_dev, words64, mask_of, scores_out, rows_out, st);
+    if (int rc = search_masks_impl(h, q_dev, B, k, masks_dev, words64, of_dev, mask_of, out[0].as<float>(),
+                                   out[1].as<int64_t>(), st))
         return rc;
-    HIP_TRY(hipMemcpyAsync(scores_out, s_dev, (size_t)B * k * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(rows_out, r_dev, (size_t)B * k * 8, hipMemcpyDeviceToHost, st));
+    if (int rc = stage_download(out, st)) return rc;
     HIP_TRY(hipStreamSynchronize(st));
     return HR_OK;
 }
@@ -2059,10 +2049,9 @@ extern "C" int hr_index_search_masks(hr_index* h, const float* q, int B, int k, 
 static int sync_graph_search(hr_index* h, const float* q, int B, int k, float* scores_out, int64_t* rows_out) {
     if (int rc = shadow_update(h)) return rc;  // (a replay reads the shadow as it is now)
     hipStream_t st = h->stream;
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t qb = (size_t)B * h->dim * 4, sb = (size_t)B * k * 4, rb = (size_t)B * k * 8;
-    const size_t o_s = up(qb), o_r = o_s + up(sb), o_f = o_r + up(rb), o_k = o_f + up((size_t)B * 4);
-    const size_t total = o_k + up((size_t)B * 8);
+    const size_t o_s = up256(qb), o_r = o_s + up256(sb), o_f = o_r + up256(rb), o_k = o_f + up256((size_t)B * 4);
+    const size_t total = o_k + up256((size_t)B * 8);
     hr_index::SyncGraph* e = nullptr;
     for (auto& g : h->sync_graphs)
         if (g.B == B && g.k == k) e = &g;
@@ -2100,20 +2089,20 @@ static int sync_graph_search(hr_index* h, const float* q, int B, int k, float* s
             HIP_TRY(hipHostMalloc(&h->pin, total, hipHostMallocDefault));
             h->pin_bytes = total;
         }
-        HIP_TRY(h->q_in.ensure(qb));
-        HIP_TRY(h->sync_out.ensure(up(sb) + rb));
+        HIP_TRY(h->hs.q.ensure(qb));
+        HIP_TRY(h->sync_out.ensure(up256(sb) + rb));
         // captured on a stream of its own: a failed capture can leave its stream unusable
         hipStream_t cs = nullptr;
         HIP_TRY(index_stream_create(h, &cs, false));
         const uint64_t gen0 = g_buf_gen.load();
         uint8_t* pin = (uint8_t*)h->pin;
         float* s_dev = h->sync_out.as<float>();
-        int64_t* r_dev = (int64_t*)(h->sync_out.as<uint8_t>() + up(sb));
+        int64_t* r_dev = (int64_t*)(h->sync_out.as<uint8_t>() + up256(sb));
         const int64_t passes0 = h->main_passes;
         const bool began = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal) == hipSuccess;
         int rc = began ? HR_OK : HR_E_HIP;
-        if (!rc && hipMemcpyAsync(h->q_in.p, pin, qb, hipMemcpyHostToDevice, cs) != hipSuccess) rc = HR_E_HIP;
-        if (!rc) rc = search_main(h, h->q_in.as<float>(), B, k, nullptr, s_dev, r_dev, cs);
+        if (!rc && hipMemcpyAsync(h->hs.q.p, pin, qb, hipMemcpyHostToDevice, cs) != hipSuccess) rc = HR_E_HIP;
+        if (!rc) rc = search_main(h, h->hs.q.as<float>(), B, k, nullptr, s_dev, r_dev, cs);
         if (!rc && (hipMemcpyAsync(pin + o_s, s_dev, sb, hipMemcpyDeviceToHost, cs) != hipSuccess ||
                     hipMemcpyAsync(pin + o_r, r_dev, rb, hipMemcpyDeviceToHost, cs) != hipSuccess ||
                     hipMemcpyAsync(pin + o_f, h->fail.p, (size_t)B * 4, hipMemcpyDeviceToHost, cs) != hipSuccess ||
@@ -2164,8 +2153,8 @@ static int sync_graph_search(hr_index* h, const float* q, int B, int k, float* s
         return HR_OK;
     }
     float* s_dev = h->sync_out.as<float>();
-    int64_t* r_dev = (int64_t*)(h->sync_out.as<uint8_t>() + up(sb));
-    if (int rc = search_fallback(h, h->q_in.as<float>(), k, nullptr, s_dev, r_dev, failed, (const double*)(pin + o_k), st))
+    int64_t* r_dev = (int64_t*)(h->sync_out.as<uint8_t>() + up256(sb));
+    if (int rc = search_fallback(h, h->hs.q.as<float>(), k, nullptr, s_dev, r_dev, failed, (const double*)(pin + o_k), st))
         return rc;
     HIP_TRY(hipMemcpyAsync(scores_out, s_dev, sb, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(rows_out, r_dev, rb, hipMemcpyDeviceToHost, st));
@@ -2297,17 +2286,16 @@ extern "C" int hr_index_search_submit_host(hr_index* h, const float* q, int B, i
     if (!h->acopy) HIP_TRY(index_stream_create(h, &h->acopy, false));
     if (!sl.done) HIP_TRY(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
     if (!sl.q_ready) HIP_TRY(hipEventCreateWithFlags(&sl.q_ready, hipEventDisableTiming));
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t qb = (size_t)B * h->dim * 4;
-    sl.off_s = up(qb);
-    sl.off_r = sl.off_s + up((size_t)B * k * 4);
-    sl.off_f = sl.off_r + up((size_t)B * k * 8);
-    sl.off_k = sl.off_f + up((size_t)B * 4);
+    sl.off_s = up256(qb);
+    sl.off_r = sl.off_s + up256((size_t)B * k * 4);
+    sl.off_f = sl.off_r + up256((size_t)B * k * 8);
+    sl.off_k = sl.off_f + up256((size_t)B * 4);
     // The slot's buffers are sized once, for kAsyncPresizeB queries at HR_MAX_K (or the batch, if larger): a
     // later reallocation (hipHostFree / hipFree synchronise the device) would stall the event loop calling this
     const int Bs = std::max(B, kAsyncPresizeB);
-    const size_t need = up((size_t)Bs * h->dim * 4) + up((size_t)Bs * HR_MAX_K * 4) + up((size_t)Bs * HR_MAX_K * 8) +
-                        up((size_t)Bs * 4) + (size_t)Bs * 8;
+    const size_t need = up256((size_t)Bs * h->dim * 4) + up256((size_t)Bs * HR_MAX_K * 4) +
+                        up256((size_t)Bs * HR_MAX_K * 8) + up256((size_t)Bs * 4) + (size_t)Bs * 8;
     if (sl.off_k + (size_t)B * 8 > sl.pin_bytes) {
         if (sl.pin) HIP_TRY(hipHostFree(sl.pin));
         sl.pin = nullptr;
@@ -2517,33 +2505,29 @@ extern "C" int hr_index_search(hr_index* h, const float* q, int B, int k, const 
         const int rc = sync_graph_search(h, q, B, k, scores_out, rows_out);
         if (rc != HR_E_UNSUPPORTED) return rc;
     }
-    HIP_TRY(h->q_in.ensure((size_t)B * h->dim * 4));
-    DevBuf& so = h->stage;
+    HIP_TRY(h->hs.q.ensure((size_t)B * h->dim * 4));
+    DevBuf& so = h->hs.out;
     const size_t words = (size_t)((h->n + 63) / 64);
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t kk = (size_t)std::min(k, HR_MAX_K);  // (k > HR_MAX_K writes the host arrays directly)
-    const size_t off_r = up((size_t)B * kk * 4), off_m = off_r + up((size_t)B * kk * 8);
+    const size_t off_r = up256((size_t)B * kk * 4), off_m = off_r + up256((size_t)B * kk * 8);
     HIP_TRY(so.ensure(off_m + (row_mask ? words * 8 : 0)));
     float* s_dev = (float*)so.p;
     int64_t* r_dev = (int64_t*)((uint8_t*)so.p + off_r);
     uint64_t* m_dev = row_mask ? (uint64_t*)((uint8_t*)so.p + off_m) : nullptr;
-    HIP_TRY(hipMemcpyAsync(h->q_in.p, q, (size_t)B * h->dim * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(h->hs.q.p, q, (size_t)B * h->dim * 4, hipMemcpyHostToDevice, st));
     if (row_mask) HIP_TRY(hipMemcpyAsync(m_dev, row_mask, words * 8, hipMemcpyHostToDevice, st));
     if (k > HR_MAX_K) {
         std::vector<Cand> c((size_t)B * k);
-        if (int rc = index_exact_all(h, h->q_in.as<float>(), B, k, m_dev, c.data(), st)) return rc;
+        if (int rc = index_exact_all(h, h->hs.q.as<float>(), B, k, m_dev, c.data(), st)) return rc;
         for (size_t i = 0; i < c.size(); ++i) {
             scores_out[i] = c[i].row >= 0 ? (float)c[i].score : -INFINITY;
             rows_out[i] = c[i].row;
         }
         return HR_OK;
     }
-    struct TileListScope {
-        hr_index* h;
-        ~TileListScope() { h->tl_n = -1; }
-    } tl_scope{h};
+    TileListScope tl_scope{h};
     if (int rc = index_host_tile_list(h, (const uint32_t*)row_mask, st)) return rc;
-    if (int rc = search_device_impl(h, h->q_in.as<float>(), B, k, m_dev, s_dev, r_dev, st)) return rc;
+    if (int rc = search_device_impl(h, h->hs.q.as<float>(), B, k, m_dev, s_dev, r_dev, st)) return rc;
     HIP_TRY(hipMemcpyAsync(scores_out, s_dev, (size_t)B * k * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(rows_out, r_dev, (size_t)B * k * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -2723,7 +2707,7 @@ static int debug_approx_impl(hr_index* h, const float* q, int B, float* approx_o
     Scratch& sc = h->scr[kSyncSet];
     const int Bp = pl.Bp;
     const int64_t n_tiles = (h->n + 31) / 32;
-    HIP_TRY(h->q_in.ensure((size_t)B * h->dim * 4));
+    HIP_TRY(h->hs.q.ensure((size_t)B * h->dim * 4));
     HIP_TRY(sc.q32.ensure((size_t)Bp * h->dpad * 4));
     // (every query group's fragments: k_prep_q writes all Bp queries, the kernel below reads the first group's)
     HIP_TRY(sc.qfrag.ensure((size_t)pl.NG * h->S * pl.QB * 1024));
@@ -2731,15 +2715,15 @@ static int debug_approx_impl(hr_index* h, const float* q, int B, float* approx_o
     if (s8) {
         HIP_TRY(sc.qbias.ensure((size_t)Bp * 4));
     }
-    HIP_TRY(h->stage.ensure((size_t)Bp * n_tiles * 32 * 4 + 16));
-    HIP_TRY(hipMemcpyAsync(h->q_in.p, q, (size_t)B * h->dim * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(h->hs.out.ensure((size_t)Bp * n_tiles * 32 * 4 + 16));
+    HIP_TRY(hipMemcpyAsync(h->hs.q.p, q, (size_t)B * h->dim * 4, hipMemcpyHostToDevice, st));
     const int MT = s8 ? F16 : mfma_type(h);
     if (MT == BF16)
-        hipLaunchKernelGGL((k_prep_q<BF16>), dim3((Bp + 3) / 4), dim3(256), 0, st, h->q_in.as<float>(), B, Bp, h->dim,
+        hipLaunchKernelGGL((k_prep_q<BF16>), dim3((Bp + 3) / 4), dim3(256), 0, st, h->hs.q.as<float>(), B, Bp, h->dim,
                            h->dpad, h->S, pl.QB, h->metric, sc.q32.as<float>(), sc.qfrag.as<uint16_t>(), sc.qerr.as<double>(),
                            nullptr, 1, nullptr, nullptr, nullptr);
     else
-        hipLaunchKernelGGL((k_prep_q<F16>), dim3((Bp + 3) / 4), dim3(256), 0, st, h->q_in.as<float>(), B, Bp, h->dim,
+        hipLaunchKernelGGL((k_prep_q<F16>), dim3((Bp + 3) / 4), dim3(256), 0, st, h->hs.q.as<float>(), B, Bp, h->dim,
                            h->dpad, h->S, pl.QB, h->metric, sc.q32.as<float>(), sc.qfrag.as<uint16_t>(), sc.qerr.as<double>(),
                            nullptr, 1, nullptr, nullptr, nullptr,
                            s8 && fold8_fits(h, pl.QB) ? sc.qbias.as<float>() : nullptr,
@@ -2750,7 +2734,7 @@ static int debug_approx_impl(hr_index* h, const float* q, int B, float* approx_o
         auto kern = pl.QB == 1 ? k_debug_approx<F16, I8S, 1> : k_debug_approx<F16, I8S, 2>;
         HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         hipLaunchKernelGGL(kern, dim3((unsigned)((n_tiles + 3) / 4)), dim3(256), lds, st, h->rows8,
-                           sc.qfrag.as<uint16_t>(), h->S, n_tiles, nullptr, h->stage.as<float>(), h->scale8,
+                           sc.qfrag.as<uint16_t>(), h->S, n_tiles, nullptr, h->hs.out.as<float>(), h->scale8,
                            s8 && fold8_fits(h, pl.QB) ? sc.qbias.as<float>() : (const float*)nullptr);
         HIP_TRY(hipGetLastError());
         return HR_OK;
@@ -2766,14 +2750,14 @@ static int debug_approx_impl(hr_index* h, const float* q, int B, float* approx_o
         HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         hipLaunchKernelGGL(kern, dim3((unsigned)((n_tiles + 3) / 4)), dim3(256), lds, st, h->rows,
                            sc.qfrag.as<uint16_t>(), h->S, n_tiles, h->metric == L2 ? h->xnorm : nullptr,
-                           h->stage.as<float>(), (const float*)nullptr, (const float*)nullptr);
+                           h->hs.out.as<float>(), (const float*)nullptr, (const float*)nullptr);
         HIP_TRY(hipGetLastError());
         return HR_OK;
     });
     if (rc) return rc;
     std::vector<float> tmp((size_t)Bp * n_tiles * 32);
     std::vector<double> qerr((size_t)Bp * 4);
-    HIP_TRY(hipMemcpyAsync(tmp.data(), h->stage.p, tmp.size() * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(tmp.data(), h->hs.out.p, tmp.size() * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(qerr.data(), sc.qerr.p, qerr.size() * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     const double max_norm = std::sqrt(h->max_norm2) * (1.0 + 1e-12);
@@ -2797,9 +2781,9 @@ extern "C" int hr_index_get_rows(hr_index* h, const int64_t* rows, int64_t n, fl
 
 int index_get_rows(hr_index* h, const int64_t* rows, int64_t n, float* out) {
     if (int rc = set_device(h)) return rc;
-    HIP_TRY(h->stage.ensure((size_t)n * 8 + (size_t)n * h->dim * 4));
-    int64_t* idx = (int64_t*)h->stage.p;
-    float* o = (float*)((uint8_t*)h->stage.p + (size_t)n * 8);
+    HIP_TRY(h->hs.out.ensure((size_t)n * 8 + (size_t)n * h->dim * 4));
+    int64_t* idx = (int64_t*)h->hs.out.p;
+    float* o = (float*)((uint8_t*)h->hs.out.p + (size_t)n * 8);
     HIP_TRY(hipMemcpyAsync(idx, rows, (size_t)n * 8, hipMemcpyHostToDevice, h->stream));
     int rc = dispatch_dt(h->dtype, [&](auto dt) -> int {
         hipLaunchKernelGGL((k_gather<decltype(dt)::value>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, h->stream,
@@ -2955,8 +2939,9 @@ extern "C" void hr_index_destroy(hr_index* h) {
     for (auto& g : h->sync_graphs)
         if (g.exec) (void)hipGraphExecDestroy(g.exec);
     if (h->pin) (void)hipHostFree(h->pin);
-    for (DevBuf* b : {&h->q_in, &h->cand, &h->bound, &h->kth, &h->fail, &h->fb_cand, &h->fb_bound, &h->fb_q,
-                      &h->fb_out, &h->stage, &h->exh, &h->tl, &h->s_mask, &h->sync_out, &h->qm_masks, &h->qm_of,
+    for (DevBuf* b : {&h->hs.q, &h->cand, &h->bound, &h->kth, &h->fail, &h->fb_cand, &h->fb_bound, &h->fb_q,
+                      &h->fb_out, &h->hs.out, &h->exh, &h->tl, &h->s_mask, &h->sync_out, &h->hs.aux, &h->hs.mask, &h->hs.of,
+                      &h->pool_s, &h->pool_r,
                       &h->ivf_coarse, &h->ivf_probe, &h->ivf_units, &h->ivf_uoff, &h->ivf_out})
         b->release();
     for (auto& sc : h->scr) sc.release_all();

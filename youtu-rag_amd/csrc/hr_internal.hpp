@@ -1,5 +1,9 @@
 // hr_internal.hpp -- host-side internals shared by the libhiprag.so translation units
-// (hr_index.hip: index handles and the exact search; hr_ivf.hip: the IVF lists search).
+// (hr_index.hip: index handles and the exact search; hr_ivf.hip: the IVF lists search; the derived searches
+// hr_collapse / hr_mmr / hr_range / hr_examples / hr_fuse .hip).  Shared here: the error macro, DevBuf and up256,
+// the index handle with its ONE host-form staging area (HostStage) and inner-search pool (pool_s / pool_r), the
+// staging helpers every host form is written in (stage_queries, stage_mask, stage_masks, stage_out /
+// stage_download), TileListScope, and the fp32 / int64 padding launcher (pad_results, hr_exhaustive.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <unistd.h>
@@ -63,7 +67,22 @@ struct DevBuf {
     }
 };
 
+inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// Staging of the host forms (host queries / masks in, host results out): ONE set per handle.  Every host form runs
+// under h->mu and none calls another, so no two are live at once.  Nothing an *_impl ensures lives here: a pointer
+// taken from these buffers stays valid for the whole call.
+struct HostStage {
+    DevBuf q,   // the queries (hr_index_search's graph path captures its address: see SyncGraph)
+        aux,    // a second per-query input (range search: the thresholds)
+        mask,   // one row mask, or D bitmaps words64 apart
+        of,     // mask_of of the D bitmaps
+        out;    // one result block of 256-byte aligned segments (stage_out); hr_index.hip's row staging
+};
+
 namespace hr {  // hr_exhaustive.hip
+// n slots of -inf / -1 (k_pad_results), at most 2^30 per launch
+int pad_results(float* s_out, int64_t* r_out, int64_t n, hipStream_t st);
 // the exhaustive pass's first half on its own (k_exact_all): keys[r] = d2key(canonical fp64 score of row r), 0 for
 // a deleted or masked-out row, vals[r] = r, for r in [0, n); the collapsed search's stage 2 reduces them by group
 int exact_all_keys(const uint8_t* rows, int dtype, int S, int dpad, const float* qv, int metric, double qn2,
@@ -210,7 +229,9 @@ struct hr_index {
     int64_t tl_n = -1;
     std::vector<uint32_t> tl_host;
     // search workspace
-    DevBuf q_in, cand, bound, kth, fail, fb_cand, fb_bound, fb_q, fb_out, stage, exh;
+    HostStage hs;
+    DevBuf pool_s, pool_r;  // the derived searches' inner search: its B x P scores / rows (one at a time under mu)
+    DevBuf cand, bound, kth, fail, fb_cand, fb_bound, fb_q, fb_out, exh;
     DevBuf ivf_coarse, ivf_probe, ivf_units, ivf_uoff, ivf_out;  // IVF lists search (hr_ivf.hip)
     Scratch scr[3];
     int flip = 0;                     // next ping-pong set of the pipelined path
@@ -220,7 +241,6 @@ struct hr_index {
     int64_t n_wide = 0;               // 128-query FILTER launches issued (hr_wide.hip; not graph replays)
     int64_t n_q256 = 0;               // 256-query FILTER launches issued (hr_q256.hip)
     int64_t n_qmask = 0;              // FILTER launches that ran with per-query masks (hr_index_search_masks)
-    DevBuf qm_masks, qm_of;           // hr_index_search_masks (host form): the D bitmaps and mask_of on the device
     bool qmask_timing = false;        // hr_index_set_qmask_timing: HIP events around the mask prep of every chunk
     hipEvent_t qm_ev[3] = {nullptr, nullptr, nullptr};
     double qm_ms[2] = {0.0, 0.0};     // union + tile list, allow table: summed over the most recent call's chunks
@@ -295,34 +315,31 @@ struct hr_index {
     int32_t* groups = nullptr;
     int64_t groups_cap = 0;
     int64_t n_groups = 0;
-    DevBuf col_q, col_mask, col_s, col_r, col_flag, col_out;  // host queries / mask, probe results, flags, host results
+    DevBuf col_flag;                  // the probe's incomplete flags
     DevBuf col_keys, col_g, col_top;  // stage 2: score keys + rows of one query (12 n bytes), group tables, top-k
     int64_t n_collapse_probe = 0, n_collapse_all = 0;  // queries answered from the probe / by the all-rows pass
     bool collapse_timing = false;     // hr_index_set_collapse_timing: HIP events around the stages of every call
     hipEvent_t col_ev[4] = {nullptr, nullptr, nullptr, nullptr};
     double col_ms[3] = {0.0, 0.0, 0.0};  // probe search, prefix kernel, stage 2 of the most recent timed call
-    // ---- MMR search (hr_mmr.hip): the probe's pool and the host form's staging; allocated by the first call
-    DevBuf mmr_q, mmr_mask, mmr_s, mmr_r, mmr_out;  // host queries / mask, pool scores / rows, host results
+    // ---- MMR search (hr_mmr.hip)
     bool mmr_timing = false;          // hr_index_set_mmr_timing: HIP events around the two stages of every call
     hipEvent_t mmr_ev[3] = {nullptr, nullptr, nullptr};
     double mmr_ms[2] = {0.0, 0.0};    // probe search, selection kernel of the most recent timed call
     // ---- range search (hr_range.hip): every buffer allocated by the first call that needs it.  rng_arena: per query
     // of a chunk one region of cap float2 scan records and cap score keys; rng_keys: stage 2's score keys + rows of
     // ONE query (12 n bytes) or a large region's row-ordered copy; rng_sort: the hits of one query being sorted
-    DevBuf rng_q, rng_t, rng_mask, rng_out, rng_arena, rng_flag, rng_keys, rng_sort, rng_tmp;
+    DevBuf rng_arena, rng_flag, rng_keys, rng_sort, rng_tmp;
     int64_t n_range_window = 0, n_range_all = 0;  // queries answered by stage 1 (window scan) / stage 2 (all rows)
     int64_t n_range_scans = 0;                    // window-scan launches (one per chunk of queries)
     DevBuf rng_wtiles;                            // diagnostics: tiles each wave of the most recent window scan scanned
     int64_t rng_waves = 0;                        // ... and how many waves that launch had (all query groups)
     // ---- search by example (hr_examples.hip): every buffer allocated by the first call that needs it.  ex_list: one
     // call's example lists as one block (offsets | rows | weights), packed in ex_host and copied once
-    DevBuf ex_list, ex_qin, ex_q, ex_mask, ex_s, ex_r, ex_cand, ex_out;  // lists, host base queries, built queries,
-                                                                        // host mask, K' results / records, host results
+    DevBuf ex_list, ex_q, ex_cand;  // lists, built queries, K' records of the exhaustive pass
     std::vector<uint8_t> ex_host;
     // ---- fused multi-query search (hr_fuse.hip): every buffer allocated by the first call that needs it.  fu_list:
     // one call's group offsets and weights as one block, packed in fu_host and copied once
-    DevBuf fu_list, fu_q, fu_masks, fu_of, fu_s, fu_r, fu_out;  // lists, host queries / bitmaps / mask_of, the members'
-                                                                // pools (scores, rows), host results
+    DevBuf fu_list;
     std::vector<uint8_t> fu_host;
 };
 
@@ -432,6 +449,76 @@ inline int set_device(hr_index* h) {
     HIP_TRY(hipSetDevice(h->device));
     return HR_OK;
 }
+
+// ---------------------------------------------------------------- host-form staging (h->hs, on st, under h->mu)
+// B host queries -> *q_dev
+inline int stage_queries(hr_index* h, const float* q, int64_t B, hipStream_t st, float** q_dev) {
+    const size_t bytes = (size_t)B * h->dim * 4;
+    HIP_TRY(h->hs.q.ensure(bytes));
+    HIP_TRY(hipMemcpyAsync(h->hs.q.p, q, bytes, hipMemcpyHostToDevice, st));
+    *q_dev = h->hs.q.as<float>();
+    return HR_OK;
+}
+// one host row mask -> *m_dev: the words that cover the index; nullptr without a mask or on an index without rows
+// (no zero-byte copy)
+inline int stage_mask(hr_index* h, const uint64_t* row_mask, hipStream_t st, uint64_t** m_dev) {
+    const size_t words = (size_t)((h->n + 63) / 64);
+    *m_dev = nullptr;
+    if (!row_mask || !words) return HR_OK;
+    HIP_TRY(h->hs.mask.ensure(words * 8));
+    HIP_TRY(hipMemcpyAsync(h->hs.mask.p, row_mask, words * 8, hipMemcpyHostToDevice, st));
+    *m_dev = h->hs.mask.as<uint64_t>();
+    return HR_OK;
+}
+// D host bitmaps, stride words apart, and the B entries of mask_of: only the words that cover the index go up,
+// words64 = (n + 63) / 64 apart on the device.  D = 0 leaves *masks_dev a valid (8-byte) address nobody reads.
+inline int stage_masks(hr_index* h, const uint64_t* masks, int D, int64_t stride, const int32_t* mask_of, int B,
+                       hipStream_t st, uint64_t** masks_dev, int32_t** of_dev) {
+    const size_t words64 = (size_t)((h->n + 63) / 64);
+    HIP_TRY(h->hs.of.ensure((size_t)B * 4));
+    HIP_TRY(h->hs.mask.ensure(std::max<size_t>(8, (size_t)D * words64 * 8)));
+    HIP_TRY(hipMemcpyAsync(h->hs.of.p, mask_of, (size_t)B * 4, hipMemcpyHostToDevice, st));
+    if (D > 0 && words64 > 0)
+        HIP_TRY(hipMemcpy2DAsync(h->hs.mask.p, words64 * 8, masks, (size_t)stride * 8, words64 * 8, (size_t)D,
+                                 hipMemcpyHostToDevice, st));
+    *masks_dev = h->hs.mask.as<uint64_t>();
+    *of_dev = h->hs.of.as<int32_t>();
+    return HR_OK;
+}
+// one result block: stage_out lays the segments out in hs.out (dev: 256-byte aligned; nullptr for a segment the
+// caller does not want, host == nullptr), stage_download copies every wanted, non-empty one to its host array
+struct OutSeg {
+    void* host;
+    size_t bytes;
+    void* dev;
+    template <class T>
+    T* as() const {
+        return (T*)dev;
+    }
+};
+template <int N>
+inline int stage_out(hr_index* h, OutSeg (&seg)[N]) {
+    size_t total = 0;
+    for (const OutSeg& s : seg) total += s.host ? up256(s.bytes) : 0;
+    HIP_TRY(h->hs.out.ensure(total));
+    size_t off = 0;
+    for (OutSeg& s : seg) {
+        s.dev = s.host ? h->hs.out.as<uint8_t>() + off : nullptr;
+        off += s.host ? up256(s.bytes) : 0;
+    }
+    return HR_OK;
+}
+template <int N>
+inline int stage_download(const OutSeg (&seg)[N], hipStream_t st) {
+    for (const OutSeg& s : seg)
+        if (s.host && s.bytes) HIP_TRY(hipMemcpyAsync(s.host, s.dev, s.bytes, hipMemcpyDeviceToHost, st));
+    return HR_OK;
+}
+// the selective-filter tile list of a host row mask (index_host_tile_list) lasts one call
+struct TileListScope {
+    hr_index* h;
+    ~TileListScope() { h->tl_n = -1; }
+};
 
 // ---------------------------------------------------------------- dispatch helpers
 template <class F>

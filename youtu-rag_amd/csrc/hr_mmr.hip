@@ -168,15 +168,6 @@ __global__ __launch_bounds__(64 * kMmrWaves) void k_mmr_select(const uint8_t* __
     }
 }
 
-__global__ void k_mmr_pad(float* __restrict__ s_out, int64_t* __restrict__ r_out, int64_t n) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    s_out[i] = -__builtin_inff();
-    r_out[i] = -1;
-}
-
-size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 int default_fetch(int k) { return std::min(HR_MAX_K, std::max(32, 4 * k)); }
 
 int check_args(hr_index* h, int B, int k, int fetch_k, double lambda) {
@@ -195,9 +186,7 @@ int mmr_impl(hr_index* h, const float* q_dev, int B, int k, int fetch_k, double 
              float* s_out, int64_t* r_out, hipStream_t st) {
     const int P = fetch_k ? fetch_k : default_fetch(k);
     if (h->n_live == 0) {  // empty index: padding, as hr_index_search
-        const int64_t tot = (int64_t)B * k;
-        hipLaunchKernelGGL(k_mmr_pad, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, s_out, r_out, tot);
-        HIP_TRY(hipGetLastError());
+        if (int rc = pad_results(s_out, r_out, (int64_t)B * k, st)) return rc;
         HIP_TRY(hipStreamSynchronize(st));
         return HR_OK;
     }
@@ -205,10 +194,10 @@ int mmr_impl(hr_index* h, const float* q_dev, int B, int k, int fetch_k, double 
     if (timed)
         for (auto& e : h->mmr_ev)
             if (!e) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(h->mmr_s.ensure((size_t)B * P * 4));
-    HIP_TRY(h->mmr_r.ensure((size_t)B * P * 8));
-    float* ps = h->mmr_s.as<float>();
-    int64_t* pr = h->mmr_r.as<int64_t>();
+    HIP_TRY(h->pool_s.ensure((size_t)B * P * 4));
+    HIP_TRY(h->pool_r.ensure((size_t)B * P * 8));
+    float* ps = h->pool_s.as<float>();
+    int64_t* pr = h->pool_r.as<int64_t>();
     if (timed) HIP_TRY(hipEventRecord(h->mmr_ev[0], st));
     if (int rc = index_search_locked(h, q_dev, B, P, mask_dev, ps, pr, st)) return rc;
     if (timed) HIP_TRY(hipEventRecord(h->mmr_ev[1], st));
@@ -240,7 +229,6 @@ int mmr_impl(hr_index* h, const float* q_dev, int B, int k, int fetch_k, double 
 }  // namespace
 
 void mmr_free(hr_index* h) {
-    for (DevBuf* b : {&h->mmr_q, &h->mmr_mask, &h->mmr_s, &h->mmr_r, &h->mmr_out}) b->release();
     for (auto& e : h->mmr_ev) {
         if (e) (void)hipEventDestroy(e);
         e = nullptr;
@@ -264,22 +252,15 @@ extern "C" int hr_index_search_mmr(hr_index* h, const float* q, int B, int k, in
     if (int rc = check_args(h, B, k, fetch_k, lambda)) return rc;
     if (int rc = set_device(h)) return rc;
     hipStream_t st = h->stream;
-    const size_t words = (size_t)((h->n + 63) / 64);
-    const size_t off_r = up256((size_t)B * k * 4);
-    HIP_TRY(h->mmr_q.ensure((size_t)B * h->dim * 4));
-    HIP_TRY(h->mmr_out.ensure(off_r + (size_t)B * k * 8));
+    OutSeg out[2] = {{scores_out, (size_t)B * k * 4}, {rows_out, (size_t)B * k * 8}};
+    float* q_dev = nullptr;
     uint64_t* m_dev = nullptr;
-    if (row_mask && words) {
-        HIP_TRY(h->mmr_mask.ensure(words * 8));
-        m_dev = h->mmr_mask.as<uint64_t>();
-        HIP_TRY(hipMemcpyAsync(m_dev, row_mask, words * 8, hipMemcpyHostToDevice, st));
-    }
-    HIP_TRY(hipMemcpyAsync(h->mmr_q.p, q, (size_t)B * h->dim * 4, hipMemcpyHostToDevice, st));
-    float* s_dev = h->mmr_out.as<float>();
-    int64_t* r_dev = (int64_t*)(h->mmr_out.as<uint8_t>() + off_r);
-    if (int rc = mmr_impl(h, h->mmr_q.as<float>(), B, k, fetch_k, lambda, m_dev, s_dev, r_dev, st)) return rc;
-    HIP_TRY(hipMemcpyAsync(scores_out, s_dev, (size_t)B * k * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(rows_out, r_dev, (size_t)B * k * 8, hipMemcpyDeviceToHost, st));
+    if (int rc = stage_out(h, out)) return rc;
+    if (int rc = stage_mask(h, row_mask, st, &m_dev)) return rc;
+    if (int rc = stage_queries(h, q, B, st, &q_dev)) return rc;
+    if (int rc = mmr_impl(h, q_dev, B, k, fetch_k, lambda, m_dev, out[0].as<float>(), out[1].as<int64_t>(), st))
+        return rc;
+    if (int rc = stage_download(out, st)) return rc;
     HIP_TRY(hipStreamSynchronize(st));
     return HR_OK;
 }

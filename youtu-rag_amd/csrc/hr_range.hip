@@ -204,19 +204,7 @@ __global__ __launch_bounds__(256) void k_range_zero(int64_t* __restrict__ c_out,
     if (i < B) c_out[i] = 0;
 }
 
-size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 dim3 grid_for(int64_t n) { return dim3((unsigned)std::max<int64_t>(1, (n + 255) / 256)); }
-
-int pad_results(float* s_out, int64_t* r_out, int64_t n, hipStream_t st) {
-    // (k_range_take pads max_hits slots of one query; a whole batch is B * max_hits contiguous slots of "one")
-    for (int64_t o = 0; o < n; o += (int64_t)1 << 30) {
-        const int64_t c = std::min<int64_t>(n - o, (int64_t)1 << 30);
-        hipLaunchKernelGGL(k_range_take, grid_for(c), dim3(256), 0, st, (const uint64_t*)nullptr, (const uint32_t*)nullptr,
-                           (int64_t)0, (int)c, s_out + o, r_out + o);
-    }
-    HIP_TRY(hipGetLastError());
-    return HR_OK;
-}
 
 // keys[i] / vals[i], i in [0, n), vals ascending: the exact count of the hits into *c_out, and (max_hits > 0) the
 // first max_hits of them by (key desc, val asc) with padding.  Waits for the count on the host; t: device threshold.
@@ -402,8 +390,7 @@ int range_floors(const double* qerr, const float* min_score, int B, int Bp, doub
 }
 
 void range_free(hr_index* h) {
-    for (DevBuf* b : {&h->rng_q, &h->rng_t, &h->rng_mask, &h->rng_out, &h->rng_arena, &h->rng_flag, &h->rng_keys,
-                      &h->rng_sort, &h->rng_tmp, &h->rng_wtiles})
+    for (DevBuf* b : {&h->rng_arena, &h->rng_flag, &h->rng_keys, &h->rng_sort, &h->rng_tmp, &h->rng_wtiles})
         b->release();
 }
 
@@ -434,35 +421,22 @@ extern "C" int hr_index_search_range(hr_index* h, const float* q, int B, const f
     if (int rc = check_thresholds(min_score, B)) return rc;
     if (int rc = set_device(h)) return rc;
     hipStream_t st = h->stream;
-    const size_t words = (size_t)((h->n + 63) / 64), nk = (size_t)B * max_hits;
-    const size_t off_r = up256(nk * 4), off_c = off_r + up256(nk * 8);
-    HIP_TRY(h->rng_q.ensure((size_t)B * h->dim * 4));
-    HIP_TRY(h->rng_t.ensure((size_t)B * 4));
-    HIP_TRY(h->rng_out.ensure(off_c + (size_t)B * 8));
+    const size_t nk = (size_t)B * max_hits;  // (count only: no score / row segments)
+    OutSeg out[3] = {{scores_out, nk * 4}, {rows_out, nk * 8}, {counts_out, (size_t)B * 8}};
+    float* q_dev = nullptr;
     uint64_t* m_dev = nullptr;
-    if (row_mask && words) {
-        HIP_TRY(h->rng_mask.ensure(words * 8));
-        m_dev = h->rng_mask.as<uint64_t>();
-        HIP_TRY(hipMemcpyAsync(m_dev, row_mask, words * 8, hipMemcpyHostToDevice, st));
-    }
-    HIP_TRY(hipMemcpyAsync(h->rng_q.p, q, (size_t)B * h->dim * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(h->rng_t.p, min_score, (size_t)B * 4, hipMemcpyHostToDevice, st));
-    float* s_dev = h->rng_out.as<float>();
-    int64_t* r_dev = (int64_t*)(h->rng_out.as<uint8_t>() + off_r);
-    int64_t* c_dev = (int64_t*)(h->rng_out.as<uint8_t>() + off_c);
-    struct TileListScope {  // the selective-filter tile list of a host mask, as hr_index_search
-        hr_index* h;
-        ~TileListScope() { h->tl_n = -1; }
-    } tl_scope{h};
+    if (int rc = stage_out(h, out)) return rc;
+    HIP_TRY(h->hs.aux.ensure((size_t)B * 4));
+    if (int rc = stage_mask(h, row_mask, st, &m_dev)) return rc;
+    if (int rc = stage_queries(h, q, B, st, &q_dev)) return rc;
+    HIP_TRY(hipMemcpyAsync(h->hs.aux.p, min_score, (size_t)B * 4, hipMemcpyHostToDevice, st));
+    TileListScope tl_scope{h};  // the selective-filter tile list of a host mask, as hr_index_search
     if (m_dev && h->n_live > 0)
         if (int rc = index_host_tile_list(h, (const uint32_t*)row_mask, st)) return rc;
-    if (int rc = range_impl(h, h->rng_q.as<float>(), B, h->rng_t.as<float>(), max_hits, m_dev, s_dev, r_dev, c_dev, st))
+    if (int rc = range_impl(h, q_dev, B, h->hs.aux.as<float>(), max_hits, m_dev, out[0].as<float>(),
+                            out[1].as<int64_t>(), out[2].as<int64_t>(), st))
         return rc;
-    if (max_hits > 0) {
-        HIP_TRY(hipMemcpyAsync(scores_out, s_dev, nk * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(rows_out, r_dev, nk * 8, hipMemcpyDeviceToHost, st));
-    }
-    HIP_TRY(hipMemcpyAsync(counts_out, c_dev, (size_t)B * 8, hipMemcpyDeviceToHost, st));
+    if (int rc = stage_download(out, st)) return rc;
     HIP_TRY(hipStreamSynchronize(st));
     return HR_OK;
 }

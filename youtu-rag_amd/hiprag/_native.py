@@ -401,22 +401,21 @@ class NativeIndex:
         return out
 
     # -- search
-    def search(self, q: np.ndarray, k: int, mask: np.ndarray | None = None) -> tuple[np.ndarray, np.ndarray]:
+    def _queries(self, q) -> np.ndarray:
+        """The queries of a host-form search as a contiguous float32 (B, dim) array; one query may come 1-D."""
         q = np.ascontiguousarray(q, np.float32)
         if q.ndim == 1:
             q = q[None, :]
         if q.shape[1] != self.dim:
             raise ValueError(f"query dim {q.shape[1]} != index dim {self.dim}")
+        return q
+
+    def search(self, q: np.ndarray, k: int, mask: np.ndarray | None = None) -> tuple[np.ndarray, np.ndarray]:
+        q = self._queries(q)
         B = q.shape[0]
         s = np.empty((B, k), np.float32)
         r = np.empty((B, k), np.int64)
-        m = None
-        if mask is not None:
-            m = np.ascontiguousarray(mask, np.uint64).reshape(-1)
-            n_rows = self.size()[0]
-            if len(m) * 64 < n_rows:  # the library reads one bit per index row
-                raise ValueError(f"row mask has {len(m)} words, the index {n_rows} rows "
-                                 f"(needs {(n_rows + 63) // 64})")
+        m = self._mask_words(mask)
         _check(self.lib.hr_index_search(self._h, _ptr(q), B, int(k), _ptr(m), _ptr(s), _ptr(r)))
         return s, r
 
@@ -425,11 +424,7 @@ class NativeIndex:
         array of row bitmaps (or a list of D equally long ones), ``mask_of[i]`` the bitmap of query i, -1 = none.
         Query i gets exactly what ``search(q[i], k, masks[mask_of[i]])`` gives.  A multi-device handle raises
         NotImplementedError: group the queries by mask and call search()."""
-        q = np.ascontiguousarray(q, np.float32)
-        if q.ndim == 1:
-            q = q[None, :]
-        if q.shape[1] != self.dim:
-            raise ValueError(f"query dim {q.shape[1]} != index dim {self.dim}")
+        q = self._queries(q)
         B = q.shape[0]
         of = np.ascontiguousarray(np.asarray(mask_of, np.int32).reshape(-1))
         if len(of) != B:
@@ -497,11 +492,7 @@ class NativeIndex:
                          probe: int = 0) -> tuple[np.ndarray, np.ndarray]:
         """search() with one hit per group: the best row of each of the k best groups, exactly
         (hr_index_search_collapsed).  ``probe``: rows the first stage fetches (0 = the library's default)."""
-        q = np.ascontiguousarray(q, np.float32)
-        if q.ndim == 1:
-            q = q[None, :]
-        if q.shape[1] != self.dim:
-            raise ValueError(f"query dim {q.shape[1]} != index dim {self.dim}")
+        q = self._queries(q)
         B = q.shape[0]
         s = np.empty((B, k), np.float32)
         r = np.empty((B, k), np.int64)
@@ -537,11 +528,7 @@ class NativeIndex:
         """search() diversified (hr_index_search_mmr): greedy picks of the largest lam * relevance - (1 - lam) * (max
         similarity to the rows picked so far) from the exact top-``fetch_k`` (0 = min(HR_MAX_K, max(32, 4 k))).  Rows
         in selection order, each with its plain-search score: the scores are not monotone.  lam = 1 is search()."""
-        q = np.ascontiguousarray(q, np.float32)
-        if q.ndim == 1:
-            q = q[None, :]
-        if q.shape[1] != self.dim:
-            raise ValueError(f"query dim {q.shape[1]} != index dim {self.dim}")
+        q = self._queries(q)
         B = q.shape[0]
         if int(k) <= 0 or int(k) > HR_MAX_K:  # (before the output arrays are sized by it)
             raise ValueError(f"k must be in [1, {HR_MAX_K}]")
@@ -574,11 +561,7 @@ class NativeIndex:
         (hr_index_search_range): ``(scores, rows, counts)`` -- the first min(count, max_hits) hits of every query in
         search()'s order, -inf / -1 after them, and the exact number of hits, also beyond ``max_hits``.
         ``max_hits = 0`` only counts: ``(None, None, counts)``."""
-        q = np.ascontiguousarray(q, np.float32)
-        if q.ndim == 1:
-            q = q[None, :]
-        if q.shape[1] != self.dim:
-            raise ValueError(f"query dim {q.shape[1]} != index dim {self.dim}")
+        q = self._queries(q)
         B = q.shape[0]
         t = np.ascontiguousarray(np.broadcast_to(np.asarray(min_score, np.float32).reshape(-1), (B,)))
         max_hits = int(max_hits)
@@ -717,11 +700,7 @@ class NativeIndex:
         ``masks`` / ``mask_of`` as search_masks: one row bitmap per member.  Returns ``(fused float64 (G, k), rows
         int64 (G, k), members uint32 (G, k))``, fused score descending then row ascending, -inf / -1 / 0 after the
         distinct rows; bit j of ``members`` says that member j of the group holds the row."""
-        q = np.ascontiguousarray(q, np.float32)
-        if q.ndim == 1:
-            q = q[None, :]
-        if q.shape[1] != self.dim:
-            raise ValueError(f"query dim {q.shape[1]} != index dim {self.dim}")
+        q = self._queries(q)
         off, w, md = self._fused_args(groups, k, mode, weights)
         Q, G = int(off[-1]), len(off) - 1
         if q.shape[0] != Q:
