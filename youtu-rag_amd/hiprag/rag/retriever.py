@@ -114,7 +114,7 @@ class _FusedRetrieve:
         if filters is not None:  # per-query masks: the synchronous device path (never the pipelined submit)
             ran = store.search_masks_device_sync(q, self._k, filters)
             return lambda: ran
-        tables = (store._records, store._metas, store._epoch)
+        tables = store._tables()
         idx, n_live = store._index, store.count_sync()
         B, k = q.shape[0], self._k
         if idx is None or n_live == 0 or k <= 0:
@@ -136,7 +136,8 @@ class _FusedRetrieve:
     def _sharded(self, idx, B):
         from .. import _native
 
-        if not hasattr(idx, "search_shard") or len(getattr(idx, "devices", (0,))) > 1 or self._k > _native.HR_MAX_K:
+        store = self.r.vector_store
+        if not hasattr(idx, "search_shard") or not store._single_device(idx) or self._k > _native.HR_MAX_K:
             return None
         if self._searcher is None or self._searcher[0] is not idx or self._searcher[1].max_batch < B:
             import torch

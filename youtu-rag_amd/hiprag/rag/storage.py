@@ -185,8 +185,7 @@ def search_examples_host(idx, examples, k: int, weights, q=None, mask=None, keep
     built = build_queries_host(idx, examples, weights, q)
     depth = 0 if keep else max((len(e) for e in examples), default=0)
     s, r = idx.search(built, int(k) + depth, mask)
-    out_s = np.full((len(examples), int(k)), -np.inf, np.float32)
-    out_r = np.full((len(examples), int(k)), -1, np.int64)
+    out_s, out_r = _padded(len(examples), int(k))
     for b, e in enumerate(examples):
         stay = r[b] >= 0
         if not keep:
@@ -287,6 +286,31 @@ class _ObjColumn:
         self.n += 1
 
 
+class _Prep(NamedTuple):
+    """One batch of a top-k search as _prep_search checked it: (B, dim) fp32 queries, top_k, the batch's one
+    where-clause or a list with one (or None) per query, and its mode: plain, one hit per group (collapse), or
+    maximal marginal relevance (mmr: the checked (lambda, pool size) of _mmr_mode)."""
+    q: np.ndarray
+    top_k: int
+    filters: Any
+    collapse: bool = False
+    mmr: tuple | None = None
+
+
+class _Pending(NamedTuple):
+    """One queued query of the micro-batcher; queries of one mode -- the (collapse, mmr) of _Prep -- and one key
+    (_filter_key(filters)) share a launch."""
+    q: np.ndarray
+    top_k: int
+    filters: Any
+    key: str
+    fut: asyncio.Future
+    mode: tuple
+
+
+_PLAIN = (False, None)  # the mode of a plain query
+
+
 class _SearchBatcher:
     """Coalesces concurrent ``search`` calls into batched launches (one per filter group; with
     ``index_params.mixed_filters`` one launch takes plain queries of any filters, each with its own row mask).
@@ -324,15 +348,12 @@ class _SearchBatcher:
         if self._drain_loop is not None and self._drain_loop is not loop and self._drain_loop.is_closed():
             self._recover_from_closed_loop(loop)
         fut = loop.create_future()
-        # collapsed and plain queries never share a launch: the flag is part of the group key
-        key = _filter_key(filters)
-        if mmr is not None:
-            # MMR queries (mmr = ("mmr", lambda, fetch_k), _mmr_mode) share a launch with MMR queries of the same
-            # lambda, pool size and filter only -- of any top_k: a k'-pick answer is the prefix of the k-pick one, so
-            # the launch runs at the batch's largest top_k and _drain cuts each query's list to its own
-            self.pending.append((q, int(top_k), filters, ("mmr", mmr[1], mmr[2], key), fut, mmr))
-        else:
-            self.pending.append((q, int(top_k), filters, "collapse\0" + key if collapse else key, fut, bool(collapse)))
+        # the mode is part of the group key: collapsed and plain queries never share a launch, and MMR queries
+        # (mmr = (lambda, pool size), _mmr_mode) share one with MMR queries of the same lambda, pool size and filter
+        # only -- of any top_k: a k'-pick answer is the prefix of the k-pick one, so the launch runs at the batch's
+        # largest top_k and _drain cuts each query's list to its own
+        mode = _PLAIN if mmr is None and not collapse else (bool(collapse), mmr)
+        self.pending.append(_Pending(q, int(top_k), filters, _filter_key(filters), fut, mode))
         if not self.running:
             self.running, self._drain_loop = True, loop
             # start draining on the next loop iteration: every task that is ready now enqueues first
@@ -354,20 +375,20 @@ class _SearchBatcher:
                 os.eventfd_read(self.efd)  # (the collects waited for every notify of those launches)
         self._native.clear()
         self._loop = None  # its reader went with the closed loop; native_fd registers one with `loop`
-        self.pending = [e for e in self.pending if e[4].get_loop() is loop]
+        self.pending = [e for e in self.pending if e.fut.get_loop() is loop]
         self.running, self._drain_loop = False, None
 
     def _take(self):
-        key = self.pending[0][3]
+        first = self.pending[0]
         # mixed_filters: a launch of plain queries fills across filter keys (the batch then carries one filter per
         # query, HipVectorStore._run_mixed); collapsed and MMR queries keep one launch per filter group and never share
         # a launch with plain ones or with each other.  The rule is unconditional: the per-query-mask call beat one launch per filter at
         # every point of the sweep (2 to 64 filters, 0.1 % to 30 % of the rows each, 1M and 10M rows: CHANGELOG.md);
         # a launch whose queries share one filter takes the single-mask search (_prep_search)
-        mixed = self.store.mixed_filters and not self.pending[0][5]
+        mixed = self.store.mixed_filters and first.mode == _PLAIN
         batch, rest = [], []
         for e in self.pending:
-            same = (not e[5]) if mixed else e[3] == key
+            same = e.mode == _PLAIN if mixed else e.key == first.key and e.mode == first.mode
             (batch if same and len(batch) < self.max_batch else rest).append(e)
         self.pending = rest
         return batch
@@ -375,15 +396,15 @@ class _SearchBatcher:
     @staticmethod
     def _batch_filters(batch):
         """The filters of a batch: the one where-clause its queries share, else one per query."""
-        if all(e[3] == batch[0][3] for e in batch):
-            return batch[0][2]
-        return [e[2] for e in batch]
+        if all(e.key == batch[0].key for e in batch):
+            return batch[0].filters
+        return [e.filters for e in batch]
 
     @staticmethod
     def _fail(batch, exc):
         for e in batch:
-            if not e[4].done():
-                e[4].set_exception(exc)
+            if not e.fut.done():
+                e.fut.set_exception(exc)
 
     # -- native completions
     def native_fd(self, loop) -> int:
@@ -442,14 +463,10 @@ class _SearchBatcher:
                 while self.pending and len(inflight) < self.depth:
                     batch = self._take()
                     try:
-                        qs = np.stack([e[0] for e in batch])
-                        k = max(e[1] for e in batch)
+                        qs = np.stack([e.q for e in batch])
+                        k = max(e.top_k for e in batch)
                         self.launches += 1
-                        mode = batch[0][5]  # False, True (collapsed) or the MMR mode tuple
-                        if isinstance(mode, tuple):
-                            prep = self.store._prep_search(qs, k, self._batch_filters(batch), mmr=mode)
-                        else:
-                            prep = self.store._prep_search(qs, k, self._batch_filters(batch), collapse=mode)
+                        prep = self.store._prep_search(qs, k, self._batch_filters(batch), *batch[0].mode)
                         aw, info = self._launch(loop, prep)
                     except Exception as exc:  # noqa: BLE001 -- this batch's waiters see the failure
                         self._fail(batch, exc)
@@ -476,8 +493,8 @@ class _SearchBatcher:
                         self._fail(batch, exc)
                         continue
                     for e, r in zip(batch, res):
-                        if not e[4].done():
-                            e[4].set_result(r if len(r) <= e[1] else r[: e[1]])
+                        if not e.fut.done():
+                            e.fut.set_result(r if len(r) <= e.top_k else r[: e.top_k])
                 batch = []
         except BaseException as exc:  # never leave a waiter hanging: fail what this drain holds
             err = exc if isinstance(exc, Exception) else RuntimeError(f"search batcher stopped: {exc!r}")
@@ -494,6 +511,34 @@ def _filter_key(filters) -> str:
     if not filters:
         return ""
     return json.dumps(filters, sort_keys=True, default=repr)
+
+
+def _as_queries(q, dim: int | None) -> np.ndarray:
+    """One query embedding or a batch of them as (B, dim) fp32 (dim None: any width)."""
+    q = np.asarray(q, dtype=np.float32)
+    if q.ndim == 1:
+        q = q[None, :]
+    if dim is not None and q.shape[1] != dim:
+        raise ValueError(f"query dim {q.shape[1]} != collection dim {dim}")
+    return q
+
+
+def _per_query_filters(filters, n: int):
+    """``filters`` as the searches run it: one where-clause (or None) for the whole batch as it is; a list / tuple with
+    one per query checked against the n queries -- the one clause where all agree (the single-mask search), else the
+    list."""
+    if isinstance(filters, (list, tuple)):
+        filters = list(filters)
+        if len(filters) != n:
+            raise ValueError(f"{len(filters)} filters for {n} queries")
+        if len({_filter_key(f) for f in filters}) == 1:
+            filters = filters[0] or None
+    return filters
+
+
+def _padded(n: int, width: int):
+    """(scores, rows) of n queries with no hits yet: -inf fp32 / -1 int64."""
+    return np.full((n, width), -np.inf, np.float32), np.full((n, width), -1, np.int64)
 
 
 class HipVectorStore(BaseVectorStore):
@@ -1018,15 +1063,12 @@ class HipVectorStore(BaseVectorStore):
         plain-search score: the scores are not monotone down the list.  Not combined with ``collapse``; ``fetch_k``
         without ``mmr_lambda`` means nothing."""
         mmr = self._mmr_mode(top_k, mmr_lambda, fetch_k, collapse)
-        if mmr is not None:
-            prep = self._prep_search(query_embeddings, top_k, filters, mmr=mmr)
-        else:
-            prep = self._prep_search(query_embeddings, top_k, filters, collapse=collapse)
+        prep = self._prep_search(query_embeddings, top_k, filters, collapse, mmr)
         return self._assemble(prep, self._run_search(prep))
 
     @staticmethod
     def _mmr_mode(top_k: int, mmr_lambda, fetch_k, collapse: bool):
-        """None for a search without ``mmr_lambda``, else its checked mode ("mmr", lambda, pool size): every limit of
+        """None for a search without ``mmr_lambda``, else its checked (lambda, pool size): every limit of
         hr_index_search_mmr is checked here, before a query is queued, so a bad one fails alone."""
         if mmr_lambda is None:
             return None
@@ -1040,7 +1082,21 @@ class HipVectorStore(BaseVectorStore):
         pool = min(top, max(32, 4 * k)) if fetch_k is None else int(fetch_k)
         if pool < max(k, 1) or pool > top:
             raise ValueError(f"fetch_k must be in [top_k, {top}] (got {fetch_k}, top_k = {top_k})")
-        return ("mmr", lam, pool)
+        return lam, pool
+
+    @staticmethod
+    def _check_collapsed_k(top_k):
+        if int(top_k) > _native.HR_MAX_K:
+            raise ValueError(f"a collapsed search returns at most {_native.HR_MAX_K} groups (top_k = {top_k})")
+
+    @staticmethod
+    def _single_device(idx) -> bool:
+        """The handle keeps its rows on one GPU (an index that does not say so does)."""
+        return len(getattr(idx, "devices", (0,))) == 1
+
+    def _tables(self):
+        """The host tables a search resolves its rows through, and the epoch they belong to."""
+        return (self._records, self._metas, self._epoch)
 
     def keyword_search_batch(self, queries: list[str], top_k: int = 5, filters: dict[str, Any] | None = None
                              ) -> list[list[tuple[Chunk, float]]]:
@@ -1052,7 +1108,7 @@ class HipVectorStore(BaseVectorStore):
             raise ValueError("keyword search needs index_params.lexical = true")
         queries = list(queries)
         with self._lock:
-            tables = (self._records, self._metas, self._epoch)
+            tables = self._tables()
             n_live = self.count_sync()
             if self._lex is None or n_live == 0 or int(top_k) <= 0 or not queries:
                 return [[] for _ in queries]
@@ -1069,41 +1125,26 @@ class HipVectorStore(BaseVectorStore):
     # search_batch in three steps, so the micro-batcher can run only the middle one in a worker thread
     # (it holds the GIL for little but the ctypes call; a worker doing the Python parts was starved by
     # a busy event loop) and assemble on the event-loop thread while the next launch runs
-    def _prep_search(self, query_embeddings, top_k: int, filters, collapse: bool = False, mmr: tuple | None = None):
-        """(q, top_k, filters) of a plain search; a fourth entry carries another mode: True = collapsed, the
-        ("mmr", lambda, pool size) tuple of _mmr_mode = MMR."""
-        q = np.asarray(query_embeddings, dtype=np.float32)
-        if q.ndim == 1:
-            q = q[None, :]
-        dim = self.dim
-        if dim is not None and q.shape[1] != dim:
-            raise ValueError(f"query dim {q.shape[1]} != collection dim {dim}")
-        if isinstance(filters, (list, tuple)):  # one where-clause (or None) per query
-            filters = list(filters)
-            if len(filters) != q.shape[0]:
-                raise ValueError(f"{len(filters)} filters for {q.shape[0]} queries")
-            keys = {_filter_key(f) for f in filters}
-            if len(keys) == 1:  # one predicate for the whole batch: the single-mask search
-                filters = filters[0] or None
-        if mmr is not None:
-            return (q, int(top_k), filters, mmr)
-        return (q, int(top_k), filters, True) if collapse else (q, int(top_k), filters)
+    def _prep_search(self, query_embeddings, top_k: int, filters, collapse: bool = False, mmr: tuple | None = None
+                     ) -> _Prep:
+        """The checked batch of a top-k search; mmr: the (lambda, pool size) of _mmr_mode."""
+        q = _as_queries(query_embeddings, self.dim)
+        return _Prep(q, int(top_k), _per_query_filters(filters, q.shape[0]), bool(collapse), mmr)
 
     def _run_mmr(self, q, top_k: int, filters, n_live: int, mmr: tuple):
-        """The native MMR search (store lock held, rows present); mmr: the checked mode of _mmr_mode."""
+        """The native MMR search (store lock held, rows present); mmr: the (lambda, pool size) of _mmr_mode."""
         idx = self._index
-        if len(getattr(idx, "devices", (0,))) > 1:
+        if not self._single_device(idx):
             raise ValueError("an MMR search needs a single-device store")
         if not hasattr(idx, "search_mmr"):
             raise NotImplementedError(f"{type(idx).__name__} has no MMR search")
-        return idx.search_mmr(q, min(top_k, n_live), mmr[1], self.filter_bitmap(filters), mmr[2])
+        return idx.search_mmr(q, min(top_k, n_live), mmr[0], self.filter_bitmap(filters), mmr[1])
 
     def _run_collapsed(self, q, top_k: int, filters, n_live: int):
         """The collapsed native search (store lock held, rows present)."""
-        if top_k > _native.HR_MAX_K:
-            raise ValueError(f"a collapsed search returns at most {_native.HR_MAX_K} groups (top_k = {top_k})")
+        self._check_collapsed_k(top_k)
         idx = self._index
-        if len(getattr(idx, "devices", (0,))) > 1:
+        if not self._single_device(idx):
             raise ValueError("a collapsed search needs a single-device store")
         if not hasattr(idx, "search_collapsed") or not hasattr(idx, "set_groups"):
             raise NotImplementedError(f"{type(idx).__name__} has no collapsed search")
@@ -1111,8 +1152,8 @@ class HipVectorStore(BaseVectorStore):
         return idx.search_collapsed(q, min(top_k, n_live), self.filter_bitmap(filters))
 
     def _distinct_filters(self, filters: list):
-        """(clauses, clause_of, bitmaps) of a per-query filter list: its distinct where-clauses in first-use order
-        (None = no filter), each query's clause, and the clauses' row bitmaps through the filter cache."""
+        """(clause_of, bitmaps) of a per-query filter list: each query's where-clause as its number among the distinct
+        ones, in first-use order, and the distinct clauses' row bitmaps through the filter cache (None = no filter)."""
         order: dict[str, int] = {}
         clauses, clause_of = [], np.empty(len(filters), np.int32)
         for i, f in enumerate(filters):
@@ -1121,10 +1162,10 @@ class HipVectorStore(BaseVectorStore):
                 order[key] = len(clauses)
                 clauses.append(f or None)
             clause_of[i] = order[key]
-        return clauses, clause_of, [self.filter_bitmap(f) for f in clauses]
+        return clause_of, [self.filter_bitmap(f) for f in clauses]
 
     @staticmethod
-    def _stack_bitmaps(bitmaps: list, clause_of):
+    def _stack_bitmaps(clause_of, bitmaps: list):
         """(masks, mask_of) for search_masks: the bitmaps that exist stacked into one (D, words) uint64 array and, per
         query, its row of that array (-1 for a query without a filter)."""
         slot, rows = np.full(len(bitmaps), -1, np.int32), []
@@ -1139,58 +1180,67 @@ class HipVectorStore(BaseVectorStore):
 
     def _takes_masks(self, idx) -> bool:
         """The index answers per-query masks in one call: a single-device exact index with search_masks."""
-        return hasattr(idx, "search_masks") and not self.ivf and len(getattr(idx, "devices", (0,))) == 1
+        return hasattr(idx, "search_masks") and not self.ivf and self._single_device(idx)
 
-    def _run_mixed(self, q, top_k: int, filters: list, n_live: int, collapse: bool):
+    def _per_clause(self, distinct, width: int, call):
+        """A per-query filter list on a call that takes one row mask: ``call(sel, bitmap) -> (scores, rows)`` once per
+        distinct where-clause (`distinct`: the list's _distinct_filters), for the queries `sel` that carry it -- so
+        ``filters[sel[0]]`` is the clause -- scattered back in query order into (B, width) arrays padded with -inf /
+        -1.  An answer narrower than `width` fills its first columns; one without lists (None, None) fills none."""
+        clause_of, bitmaps = distinct
+        scores, rows = _padded(len(clause_of), width)
+        for c, bitmap in enumerate(bitmaps):
+            sel = np.nonzero(clause_of == c)[0]
+            s, r = call(sel, bitmap)
+            self.grouped_launches += 1
+            if s is not None:
+                scores[sel, : s.shape[1]], rows[sel, : r.shape[1]] = s, r
+        return scores, rows
+
+    def _run_mixed(self, q, top_k: int, filters: list, n_live: int, collapse: bool = False, mmr: tuple | None = None):
         """A batch with one where-clause (or None) per query (store lock held, rows present).  Distinct predicates
         resolve to bitmaps through the filter cache; a single-device exact index answers the batch with ONE
         per-query-mask call (NativeIndex.search_masks).  Multi-device handles, IVF_FLAT stores and collapsed batches
         keep one launch per distinct filter, scattered back in query order -- the same results -- and so do MMR
-        batches (collapse: False, True, or the MMR mode tuple)."""
+        batches."""
         idx = self._index
         k = min(top_k, n_live)
-        clauses, mask_of, bitmaps = self._distinct_filters(filters)
-        mmr = collapse if isinstance(collapse, tuple) else None
-        collapse = collapse is True
+        distinct = self._distinct_filters(filters)
         if not collapse and mmr is None and self._takes_masks(idx):
             try:
-                out = idx.search_masks(q, k, *self._stack_bitmaps(bitmaps, mask_of))
+                out = idx.search_masks(q, k, *self._stack_bitmaps(*distinct))
                 self.mixed_launches += 1
                 return out
             except NotImplementedError:
                 pass  # (a handle that cannot take per-query masks: group below)
-        if collapse and top_k > _native.HR_MAX_K:
-            raise ValueError(f"a collapsed search returns at most {_native.HR_MAX_K} groups (top_k = {top_k})")
-        scores = np.full((len(filters), k), -np.inf, np.float32)
-        rows_out = np.full((len(filters), k), -1, np.int64)
-        for c, f in enumerate(clauses):
-            sel = np.nonzero(mask_of == c)[0]
-            if collapse:
-                s, r = self._run_collapsed(q[sel], top_k, f, n_live)
-            elif mmr is not None:
-                s, r = self._run_mmr(q[sel], top_k, f, n_live, mmr)
-            else:
-                s, r = idx.search(q[sel], k, bitmaps[c])
-            self.grouped_launches += 1
-            scores[sel, : s.shape[1]], rows_out[sel, : r.shape[1]] = s, r
-        return scores, rows_out
+        if collapse:
+            self._check_collapsed_k(top_k)
 
-    def _run_search(self, prep):
+        def call(sel, bitmap):
+            if collapse:
+                return self._run_collapsed(q[sel], top_k, filters[sel[0]], n_live)
+            if mmr is not None:
+                return self._run_mmr(q[sel], top_k, filters[sel[0]], n_live, mmr)
+            return idx.search(q[sel], k, bitmap)
+
+        return self._per_clause(distinct, k, call)
+
+    def _run_search(self, prep: _Prep):
         """The native search, under the store lock.  Everything that depends on the collection's
         current state -- the live row count, the filter bitmap (sized to the index's rows NOW, not when
         the query was queued: rows added in between would otherwise make the bitmap too short), the
         tables the rows resolve through -- is taken here, under the same lock as the search."""
-        q, top_k, filters = prep[:3]
+        q, top_k, filters = prep.q, prep.top_k, prep.filters
         with self._lock:  # ordered against mutations
-            tables = (self._records, self._metas, self._epoch)
+            tables = self._tables()
             n_live = self.count_sync()
             if self._index is None or n_live == 0 or top_k <= 0:
                 return None, tables
             if isinstance(filters, list):
-                return self._run_mixed(q, top_k, filters, n_live, len(prep) > 3 and prep[3]), tables
-            if len(prep) > 3 and isinstance(prep[3], tuple):
-                return self._run_mmr(q, top_k, filters, n_live, prep[3]), tables
-            if len(prep) > 3 and prep[3]:
+                return self._run_mixed(q, top_k, filters, n_live, prep.collapse, prep.mmr), tables
+            if prep.mmr is not None:
+                return self._run_mmr(q, top_k, filters, n_live, prep.mmr), tables
+            if prep.collapse:
                 return self._run_collapsed(q, top_k, filters, n_live), tables
             # top_k beyond the live rows returns them all (Chroma/FAISS); beyond HR_MAX_K the native
             # search takes its exhaustive exact path (same results, one corpus pass per query)
@@ -1200,80 +1250,83 @@ class HipVectorStore(BaseVectorStore):
         """(raw, tables) of an unfiltered search of the queries in `q`, a (B, dim) float32 torch tensor that may live
         on the GPU (the in-process embedder's output): the native search reads it in place and only the B * k results
         come back to the host -- no query vectors through host memory (the fused retrieve, retriever.py).  Pass the
-        result with prep = (q, top_k, None) to _assemble.  An index without a device entry point (tests) gets a host
-        copy."""
-        import torch
-
-        if q.dim() != 2 or (self.dim is not None and q.shape[1] != self.dim):
-            raise ValueError(f"queries must be (B, {self.dim})")
-        with self._lock:  # ordered against mutations, as _run_search
-            tables = (self._records, self._metas, self._epoch)
-            n_live = self.count_sync()
-            idx = self._index
-            if idx is None or n_live == 0 or top_k <= 0:
-                return None, tables
-            k = min(int(top_k), n_live)
-            if (not q.is_cuda or not hasattr(idx, "search_device") or k > _native.HR_MAX_K
-                    or len(getattr(idx, "devices", (0,))) > 1):
-                return idx.search(q.detach().cpu().numpy(), k, None), tables
-            q = q.to(torch.float32).contiguous()
-            B = q.shape[0]
-            ns = (B * k + 1) // 2 * 2  # scores, then the rows 8-byte aligned: one buffer, one copy back
-            out = torch.empty((ns + 2 * B * k,), dtype=torch.float32, device=q.device)
-            s_out, r_out = out[:B * k], out[ns:].view(torch.int64)
-            st = torch.cuda.current_stream(q.device)
-            idx.search_device(q.data_ptr(), B, k, s_out.data_ptr(), r_out.data_ptr(), stream=st.cuda_stream)
-            host = out.cpu().numpy()  # (after the search, on the same stream)
-            return (host[:B * k].reshape(B, k).copy(), host[ns:].view(np.int64).reshape(B, k).copy()), tables
+        result with the _prep_search of the same queries to _assemble.  An index without a device entry point (tests)
+        gets a host copy."""
+        return self._search_device(q, top_k, None)
 
     def search_masks_device_sync(self, q, top_k: int, filters: list):
         """search_device_sync for queries that carry one where-clause (or None) each: (raw, tables) of ONE
         per-query-mask search of the device queries in `q` (the fused retrieve on a mixed_filters store).  The bitmaps
         go up once per call; an index without the device entry point, a multi-device handle or k beyond HR_MAX_K gets
         a host copy of the queries through _run_mixed."""
+        return self._search_device(q, top_k, filters)
+
+    def _search_device(self, q, top_k: int, filters: list | None):
+        """The two device-query searches: `filters` None = unfiltered, else one where-clause (or None) per query."""
         import torch
 
         if q.dim() != 2 or (self.dim is not None and q.shape[1] != self.dim):
             raise ValueError(f"queries must be (B, {self.dim})")
-        if len(filters) != q.shape[0]:
+        if filters is not None and len(filters) != q.shape[0]:
             raise ValueError(f"{len(filters)} filters for {q.shape[0]} queries")
         with self._lock:  # ordered against mutations, as _run_search
-            tables = (self._records, self._metas, self._epoch)
+            tables = self._tables()
             n_live = self.count_sync()
             idx = self._index
             if idx is None or n_live == 0 or top_k <= 0:
                 return None, tables
             k = min(int(top_k), n_live)
-            if (not q.is_cuda or not hasattr(idx, "search_masks_device") or k > _native.HR_MAX_K
-                    or not self._takes_masks(idx)):
-                return self._run_mixed(q.detach().cpu().numpy(), int(top_k), list(filters), n_live, False), tables
-            _, clause_of, bitmaps = self._distinct_filters(list(filters))
-            masks, mask_of = self._stack_bitmaps(bitmaps, clause_of)
+            if filters is None:
+                on_device = hasattr(idx, "search_device") and self._single_device(idx)
+            else:
+                on_device = hasattr(idx, "search_masks_device") and self._takes_masks(idx)
+            if not q.is_cuda or k > _native.HR_MAX_K or not on_device:
+                q = q.detach().cpu().numpy()
+                if filters is None:
+                    return idx.search(q, k, None), tables
+                return self._run_mixed(q, int(top_k), list(filters), n_live), tables
             q = q.to(torch.float32).contiguous()
             B = q.shape[0]
+            s_out, r_out, fetch = self._device_out(q, B, k)
+            st = torch.cuda.current_stream(q.device)
+            if filters is None:
+                idx.search_device(q.data_ptr(), B, k, s_out.data_ptr(), r_out.data_ptr(), stream=st.cuda_stream)
+                return fetch(), tables
+            masks, mask_of = self._stack_bitmaps(*self._distinct_filters(list(filters)))
             m_dev = torch.from_numpy(masks.view(np.int64)).to(q.device) if masks.size else None
             of_dev = torch.from_numpy(np.ascontiguousarray(mask_of, np.int32)).to(q.device)
-            ns = (B * k + 1) // 2 * 2
-            out = torch.empty((ns + 2 * B * k,), dtype=torch.float32, device=q.device)
-            s_out, r_out = out[:B * k], out[ns:].view(torch.int64)
-            st = torch.cuda.current_stream(q.device)
             idx.search_masks_device(q.data_ptr(), B, k, s_out.data_ptr(), r_out.data_ptr(),
                                     m_dev.data_ptr() if m_dev is not None else 0, masks.shape[0], masks.shape[1],
                                     of_dev.data_ptr(), stream=st.cuda_stream)
             self.mixed_launches += 1
+            return fetch(), tables  # (m_dev, of_dev alive until the results are back)
+
+    @staticmethod
+    def _device_out(q, B: int, k: int):
+        """One device buffer for a (B, k) answer -- the fp32 scores, then the int64 rows 8-byte aligned -- as (scores
+        view, rows view, fetch): ``fetch()`` brings the buffer back in one copy (after the search, on the same stream)
+        and returns the host (scores, rows)."""
+        import torch
+
+        ns = (B * k + 1) // 2 * 2
+        out = torch.empty((ns + 2 * B * k,), dtype=torch.float32, device=q.device)
+
+        def fetch():
             host = out.cpu().numpy()
-            return (host[:B * k].reshape(B, k).copy(), host[ns:].view(np.int64).reshape(B, k).copy()), tables
+            return host[:B * k].reshape(B, k).copy(), host[ns:].view(np.int64).reshape(B, k).copy()
+
+        return out[:B * k], out[ns:].view(torch.int64), fetch
 
     def _submit_native(self, prep, batcher: _SearchBatcher, loop):
         """Launch an unfiltered batch through the asynchronous native entry point from the event loop
         (None: this batch takes the worker-thread path -- a filter, no async-capable index, k beyond
         HR_MAX_K, an empty collection, or the store / handle busy: nothing here ever waits)."""
-        if len(prep) > 3 and prep[3]:  # collapsed or MMR: the worker-thread route, as filtered batches
+        if prep.collapse or prep.mmr is not None:  # the worker-thread route, as filtered batches
             return None
-        q, top_k, filters = prep
+        q, top_k, filters = prep.q, prep.top_k, prep.filters
         idx = self._index
         if (filters or idx is None or not self.native_async or top_k <= 0 or top_k > _native.HR_MAX_K
-                or not hasattr(idx, "search_submit_host") or len(getattr(idx, "devices", (0,))) > 1):
+                or not hasattr(idx, "search_submit_host") or not self._single_device(idx)):
             return None
         if not self._lock.acquire(blocking=False):  # a mutation (in a worker thread) holds the store
             return None
@@ -1289,7 +1342,7 @@ class HipVectorStore(BaseVectorStore):
                 ticket = idx.search_submit_host(q, k, fd)
             except (NotImplementedError, _native.BusyError):
                 return None
-            return idx, ticket, q.shape[0], k, (self._records, self._metas, self._epoch)
+            return idx, ticket, q.shape[0], k, self._tables()
         finally:
             self._lock.release()
 
@@ -1315,10 +1368,12 @@ class HipVectorStore(BaseVectorStore):
         finally:
             self._lock.release()
 
-    def _gather(self, ran):
+    def _gather(self, ran, extra=None, embeddings: bool = True):
         """The host lists of a finished batch's hits -- (rec_l, meta_l, score_l, per_q, embs) -- or None when the store
         was cleared since the search ran (its rows are gone).  The hits' host records are gathered for the whole batch
-        at once (object-array fancy indexing instead of a Python lookup per row and field)."""
+        at once (object-array fancy indexing instead of a Python lookup per row and field).  `extra`: one more (B, k)
+        array of the search, returned as a sixth list of the same hits; `embeddings` False: embs None whatever
+        include_embeddings says."""
         raw, (recs, metas, epoch) = ran
         if raw is None or epoch != self._epoch:
             return None
@@ -1333,7 +1388,7 @@ class HipVectorStore(BaseVectorStore):
         score_l = scores[valid].tolist()
         per_q = valid.sum(axis=1).tolist()
         embs = None
-        if self.include_embeddings and len(hit_rows):
+        if embeddings and self.include_embeddings and len(hit_rows):
             keep = [i for i, r in enumerate(rec_l) if r is not None]
             with self._lock:
                 if epoch != self._epoch:
@@ -1342,6 +1397,8 @@ class HipVectorStore(BaseVectorStore):
             embs = [None] * len(rec_l)
             for j, i in enumerate(keep):
                 embs[i] = e[j].tolist()
+        if extra is not None:
+            return rec_l, meta_l, score_l, per_q, embs, extra[valid].tolist()
         return rec_l, meta_l, score_l, per_q, embs
 
     def _assemble(self, prep, ran) -> list[list[tuple[Chunk, float]]]:
@@ -1372,24 +1429,15 @@ class HipVectorStore(BaseVectorStore):
         if int(top_k) <= 0:
             return []
         q = np.asarray(query_embedding, dtype=np.float32).reshape(-1)
-        if mmr is not None:
-            return await self._batcher.submit(q, top_k, filters, mmr=mmr)
-        if not collapse:
-            return await self._batcher.submit(q, top_k, filters)
-        if int(top_k) > _native.HR_MAX_K:  # checked before queueing: a bad query fails alone
-            raise ValueError(f"a collapsed search returns at most {_native.HR_MAX_K} groups (top_k = {top_k})")
-        return await self._batcher.submit(q, top_k, filters, collapse=True)
+        if collapse:
+            self._check_collapsed_k(top_k)  # checked before queueing: a bad query fails alone
+        return await self._batcher.submit(q, top_k, filters, collapse, mmr)
 
     # -- range search (hr_index_search_range): every chunk scoring at least min_score, and how many
     def _prep_range(self, query_embeddings, min_score, max_hits: int, filters):
         """(q, thresholds, max_hits, filters) of a range search, every limit checked: a bad request fails here,
         before any native call."""
-        q = np.asarray(query_embeddings, dtype=np.float32)
-        if q.ndim == 1:
-            q = q[None, :]
-        dim = self.dim
-        if dim is not None and q.shape[1] != dim:
-            raise ValueError(f"query dim {q.shape[1]} != collection dim {dim}")
+        q = _as_queries(query_embeddings, self.dim)
         max_hits = int(max_hits)
         if max_hits < 0 or max_hits > _native.HR_RANGE_MAX_HITS:
             raise ValueError(f"max_hits must be in [0, {_native.HR_RANGE_MAX_HITS}] (got {max_hits})")
@@ -1399,13 +1447,8 @@ class HipVectorStore(BaseVectorStore):
         t = np.ascontiguousarray(np.broadcast_to(t, (q.shape[0],)))
         if np.isnan(t).any():
             raise ValueError("min_score must not be NaN")
-        if isinstance(filters, (list, tuple)):  # one where-clause (or None) per query
-            filters = list(filters)
-            if len(filters) != q.shape[0]:
-                raise ValueError(f"{len(filters)} filters for {q.shape[0]} queries")
-            if len({_filter_key(f) for f in filters}) == 1:
-                filters = filters[0] or None
-        if len(getattr(self._index, "devices", (0,))) > 1:
+        filters = _per_query_filters(filters, q.shape[0])
+        if not self._single_device(self._index):
             raise ValueError("a range search needs a single-device store")
         return q, t, max_hits, filters
 
@@ -1415,41 +1458,36 @@ class HipVectorStore(BaseVectorStore):
         q, t, max_hits, filters = prep
         B = q.shape[0]
         with self._lock:  # ordered against mutations
-            tables = (self._records, self._metas, self._epoch)
+            tables = self._tables()
             idx = self._index
             counts = np.zeros(B, np.int64)
             if idx is None or self.count_sync() == 0:
                 return None, counts, tables
-            if len(getattr(idx, "devices", (0,))) > 1:
+            if not self._single_device(idx):
                 raise ValueError("a range search needs a single-device store")
             if not hasattr(idx, "search_range"):
                 raise NotImplementedError(f"{type(idx).__name__} has no range search")
             if not isinstance(filters, list):
                 s, r, counts = idx.search_range(q, t, max_hits, self.filter_bitmap(filters))
                 return (None if s is None else (s, r)), np.asarray(counts, np.int64), tables
-            clauses, clause_of, bitmaps = self._distinct_filters(filters)
-            scores = np.full((B, max_hits), -np.inf, np.float32)
-            rows_out = np.full((B, max_hits), -1, np.int64)
-            for c in range(len(clauses)):
-                sel = np.nonzero(clause_of == c)[0]
-                s, r, n = idx.search_range(q[sel], t[sel], max_hits, bitmaps[c])
-                self.grouped_launches += 1
-                counts[sel] = n
-                if max_hits:
-                    scores[sel], rows_out[sel] = s, r
-            return ((scores, rows_out) if max_hits else None), counts, tables
+
+            def call(sel, bitmap):  # (a count-only call, max_hits 0, has no lists: s, r None)
+                s, r, counts[sel] = idx.search_range(q[sel], t[sel], max_hits, bitmap)
+                return s, r
+
+            raw = self._per_clause(self._distinct_filters(filters), max_hits, call)
+            return (raw if max_hits else None), counts, tables
 
     def search_range_batch(self, query_embeddings, min_score, max_hits: int = 1024, filters=None) -> list[RangeHits]:
         """Every stored chunk whose score is at least ``min_score`` (a scalar or one value per query), exactly: per
         query a RangeHits of the first ``max_hits`` hits, best first, and the exact total -- ``truncated`` tells
         whether the list was cut.  ``filters``: one where-clause, or a list with one (or None) per query."""
         prep = self._prep_range(query_embeddings, min_score, max_hits, filters)
-        raw, counts, tables = self._run_range(prep)
-        B = len(prep[0])
-        if raw is None:
-            return [RangeHits([], int(counts[b])) for b in range(B)]
-        lists = self._assemble(prep, (raw, tables))
-        return [RangeHits(lists[b], int(counts[b])) for b in range(B)]
+        return self._range_hits(prep, self._run_range(prep))
+
+    def _range_hits(self, prep, ran) -> list[RangeHits]:
+        raw, counts, tables = ran  # (raw None -- count-only, nothing stored -- assembles to empty lists)
+        return [RangeHits(hits, int(c)) for hits, c in zip(self._assemble(prep, (raw, tables)), counts)]
 
     def count_above_batch(self, query_embeddings, min_score, filters=None) -> list[int]:
         """How many stored chunks score at least ``min_score``, per query: the count-only range search."""
@@ -1462,10 +1500,7 @@ class HipVectorStore(BaseVectorStore):
         micro-batched top-k)."""
         q = np.asarray(query_embedding, dtype=np.float32).reshape(1, -1)
         prep = self._prep_range(q, min_score, max_hits, filters)  # checked here: a bad request fails alone
-        raw, counts, tables = await asyncio.to_thread(self._run_range, prep)
-        if raw is None:
-            return RangeHits([], int(counts[0]))
-        return RangeHits(self._assemble(prep, (raw, tables))[0], int(counts[0]))
+        return self._range_hits(prep, await asyncio.to_thread(self._run_range, prep))[0]
 
     # -- search by example (hr_index_search_examples; DESIGN.md 4k): "more like these chunks"
     def _prep_similar(self, positive_ids, negative_ids, top_k: int, filters, query_embeddings, pos_weight, neg_weight):
@@ -1486,20 +1521,11 @@ class HipVectorStore(BaseVectorStore):
             raise ValueError("pos_weight and neg_weight must be finite")
         q = None
         if query_embeddings is not None:
-            q = np.asarray(query_embeddings, dtype=np.float32)
-            if q.ndim == 1:
-                q = q[None, :]
+            q = _as_queries(query_embeddings, None)
             if q.shape[0] != B:
                 raise ValueError(f"{q.shape[0]} query embeddings for {B} queries")
-            dim = self.dim
-            if dim is not None and q.shape[1] != dim:
-                raise ValueError(f"query dim {q.shape[1]} != collection dim {dim}")
-        if isinstance(filters, (list, tuple)):  # one where-clause (or None) per query
-            filters = list(filters)
-            if len(filters) != B:
-                raise ValueError(f"{len(filters)} filters for {B} queries")
-            if len({_filter_key(f) for f in filters}) == 1:
-                filters = filters[0] or None
+            q = _as_queries(q, self.dim)  # (the dim after the count, as the checks always ran)
+        filters = _per_query_filters(filters, B)
         examples, weights = [], []
         with self._lock:
             for P_, N_ in zip(pos, neg):
@@ -1525,12 +1551,12 @@ class HipVectorStore(BaseVectorStore):
         examples, weights, q, top_k, filters = prep
         B = len(examples)
         with self._lock:  # ordered against mutations
-            tables = (self._records, self._metas, self._epoch)
+            tables = self._tables()
             idx, n_live = self._index, self.count_sync()
             if idx is None or n_live == 0 or top_k <= 0 or B == 0:
                 return None, tables
             k = min(top_k, n_live)
-            native = hasattr(idx, "search_examples") and len(getattr(idx, "devices", (0,))) == 1
+            native = hasattr(idx, "search_examples") and self._single_device(idx)
 
             def call(sel, bitmap):
                 ex, w = [examples[i] for i in sel], [weights[i] for i in sel]
@@ -1541,14 +1567,7 @@ class HipVectorStore(BaseVectorStore):
 
             if not isinstance(filters, list):
                 return call(np.arange(B), self.filter_bitmap(filters)), tables
-            clauses, clause_of, bitmaps = self._distinct_filters(filters)
-            scores = np.full((B, k), -np.inf, np.float32)
-            rows_out = np.full((B, k), -1, np.int64)
-            for c in range(len(clauses)):
-                sel = np.nonzero(clause_of == c)[0]
-                scores[sel], rows_out[sel] = call(sel, bitmaps[c])
-                self.grouped_launches += 1
-            return (scores, rows_out), tables
+            return self._per_clause(self._distinct_filters(filters), k, call), tables
 
     def search_similar_batch(self, positive_ids, negative_ids=None, top_k: int = 5, filters=None,
                              query_embeddings=None, pos_weight: float = 1.0, neg_weight: float = 1.0
@@ -1579,8 +1598,7 @@ class HipVectorStore(BaseVectorStore):
         every limit of hr_index_search_fused checked: a bad request fails here, before any native call."""
         if fusion not in _native.FUSE_MODES:
             raise ValueError(f"fusion must be 'rrf' or 'max' (got {fusion!r})")
-        groups = [np.asarray(g, dtype=np.float32) for g in query_groups]
-        groups = [g[None, :] if g.ndim == 1 else g for g in groups]
+        groups = [_as_queries(g, None) for g in query_groups]  # (the dim below, with the fused search's own text)
         counts = [int(g.shape[0]) for g in groups]
         if any(m < 1 or m > _native.HR_FUSE_MAX_MEMBERS or g.ndim != 2 for m, g in zip(counts, groups)):
             raise ValueError(f"a group takes 1 to {_native.HR_FUSE_MAX_MEMBERS} query embeddings")
@@ -1607,14 +1625,9 @@ class HipVectorStore(BaseVectorStore):
             w = np.asarray([v for ws in weights for v in ws], np.float64).astype(np.float32)
             if not np.isfinite(w).all():
                 raise ValueError("weights must be finite")
-        if isinstance(filters, (list, tuple)):  # one where-clause (or None) per member, in flattened order
-            filters = list(filters)
-            if len(filters) != len(q):
-                raise ValueError(f"{len(filters)} filters for {len(q)} queries")
-            if len({_filter_key(f) for f in filters}) == 1:
-                filters = filters[0] or None
-            elif not self.mixed_filters:
-                raise ValueError("one filter per member needs index_params.mixed_filters = true")
+        filters = _per_query_filters(filters, len(q))  # (a list: one where-clause or None per member, flattened)
+        if isinstance(filters, list) and not self.mixed_filters:
+            raise ValueError("one filter per member needs index_params.mixed_filters = true")
         return q, counts, k, pool, fusion, rk, w, filters
 
     def _run_fused(self, prep):
@@ -1623,54 +1636,39 @@ class HipVectorStore(BaseVectorStore):
         distinct filter -- and fuse_lists_host: the same results."""
         q, counts, k, pool, mode, rk, w, filters = prep
         with self._lock:  # ordered against mutations
-            tables = (self._records, self._metas, self._epoch)
+            tables = self._tables()
             idx, n_live = self._index, self.count_sync()
             if idx is None or n_live == 0 or k <= 0 or not counts:
                 return None, tables
-            native = hasattr(idx, "search_fused") and not self.ivf and len(getattr(idx, "devices", (0,))) == 1
-            if isinstance(filters, list):
-                clauses, clause_of, bitmaps = self._distinct_filters(filters)
-                if native:
-                    masks, mask_of = self._stack_bitmaps(bitmaps, clause_of)
+            distinct = self._distinct_filters(filters) if isinstance(filters, list) else None
+            if hasattr(idx, "search_fused") and not self.ivf and self._single_device(idx):
+                if distinct is not None:
+                    masks, mask_of = self._stack_bitmaps(*distinct)
                     self.mixed_launches += 1
-                    return idx.search_fused(q, counts, k, pool, mode, rk, w, masks, mask_of), tables
-            elif native:
-                bm = self.filter_bitmap(filters)
-                masks, mask_of = (None, None) if bm is None else (bm, np.zeros(len(q), np.int32))
+                else:
+                    bm = self.filter_bitmap(filters)
+                    masks, mask_of = (None, None) if bm is None else (bm, np.zeros(len(q), np.int32))
                 return idx.search_fused(q, counts, k, pool, mode, rk, w, masks, mask_of), tables
             depth = min(pool, n_live)  # (an index's plain search may refuse more rows than it has)
-            scores = np.full((len(q), pool), -np.inf, np.float32)
-            rows = np.full((len(q), pool), -1, np.int64)
-            if isinstance(filters, list):
-                for c in range(len(clauses)):
-                    sel = np.nonzero(clause_of == c)[0]
-                    scores[sel, :depth], rows[sel, :depth] = idx.search(q[sel], depth, bitmaps[c])
-                    self.grouped_launches += 1
+            if distinct is not None:
+                scores, rows = self._per_clause(distinct, pool, lambda sel, bitmap: idx.search(q[sel], depth, bitmap))
             else:
+                scores, rows = _padded(len(q), pool)
                 scores[:, :depth], rows[:, :depth] = idx.search(q, depth, self.filter_bitmap(filters))
             return fuse_lists_host(scores, rows, counts, k, mode, rk, w), tables
 
     def _assemble_fused(self, n_groups: int, ran) -> list[FusedHits]:
-        raw, (recs, metas, epoch) = ran
-        if raw is None or epoch != self._epoch:
+        """A finished fused batch as FusedHits: _assemble's (Chunk, score) pairs, never with embeddings, and the
+        member bits of the hits that are still stored."""
+        raw, tables = ran
+        g = None if raw is None else self._gather((raw[:2], tables), extra=raw[2], embeddings=False)
+        if g is None:
             return [FusedHits([], []) for _ in range(n_groups)]
-        fused, rows, members = raw
-        valid = (rows >= 0) & (rows < min(len(recs), len(metas)))
-        hit_rows = rows[valid]
-        rec_l, meta_l = recs.a[hit_rows].tolist(), metas.a[hit_rows].tolist()
-        score_l, mem_l, per_g = fused[valid].tolist(), members[valid].tolist(), valid.sum(axis=1).tolist()
+        rec_l, meta_l, score_l, per_g, _, mem_l = g
         out, i = [], 0
-        for cnt in per_g:
-            hits, mem = [], []
-            for j in range(i, i + cnt):
-                r = rec_l[j]
-                if r is None:  # deleted since the search ran
-                    continue
-                m = meta_l[j]
-                hits.append((Chunk(r[0], m.get("document_id", ""), r[2], m.get("chunk_index", 0), dict(m), None),
-                             score_l[j]))
-                mem.append(int(mem_l[j]))
-            out.append(FusedHits(hits, mem))
+        for hits, cnt in zip(_assemble_py(Chunk, rec_l, meta_l, score_l, per_g, None), per_g):
+            # (a hit deleted since the search ran is dropped, and its member bits with it)
+            out.append(FusedHits(hits, [m for r, m in zip(rec_l[i:i + cnt], mem_l[i:i + cnt]) if r is not None]))
             i += cnt
         return out
 
