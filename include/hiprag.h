@@ -241,6 +241,59 @@ int hr_index_search_range(hr_index* h, const float* q, int B, const float* min_s
 int hr_index_search_range_device(hr_index* h, const float* q_dev, int B, const float* min_score_dev, int max_hits,
                                  const uint64_t* row_mask_dev, float* scores_out_dev, int64_t* rows_out_dev,
                                  int64_t* counts_out_dev, void* stream);
+/* Boosted search: the exact top-k of similarity blended with per-row boosts, over the whole collection
+ * (Elasticsearch function_score / rank_feature, Qdrant's score-boosting formula, Vespa rank profiles, Milvus boost
+ * rankers; the reference's memory search re-ranks a guessed top_k window on the host with 0.5 similarity + 0.3
+ * importance + 0.2 recency, memory_toolkit.py:865-924; tests/boost_ref.py restates all of it).
+ * Boost columns: up to HR_BOOST_MAX_COLS columns of one fp32 per row.  hr_index_set_boost writes values[0, n) (HOST)
+ * to rows [row0, row0 + n) of column col.  values must be finite: a NaN or infinite value, col outside
+ * [0, HR_BOOST_MAX_COLS) or rows at or beyond the index's row count: HR_E_INVALID, all checked on the host before any
+ * device call.  A column is a device array owned by the handle: its first set allocates it (an index that never
+ * boosts pays nothing), it grows by doubling and keeps its contents, new entries are 0.0f; rows added later read 0.0
+ * until set, a column never set reads 0.0 everywhere; a range may be set again at any time.  hr_index_save does not
+ * write the columns (the caller derives them again, as the group column); hr_index_destroy frees them.
+ * Search, per query: over the live rows the mask allows, s(r) the canonical fp64 score under the index's metric (the
+ * bits the range search compares), the blended value in fp64
+ *     v(r) = (...((alpha * s(r)) + beta[0] * (double)b_0(r)) + beta[1] * (double)b_1(r)) ...)
+ * -- every product and every addition rounded once, in column order, no fused multiply-add.  The result is the first
+ * k rows by (v desc, row asc; -0.0 and 0.0 are equal and written as 0.0): blended_out holds v, scores_out (float)s(r)
+ * -- the number hr_index_search returns for that row, so similarity thresholds keep their meaning -- rows_out the
+ * row; slots past the live, allowed rows hold -inf / -inf / -1.  A row whose v is NaN is never returned.  On corpora
+ * without NaN scores, alpha = 1 with every beta zero, every referenced column all zero, or n_cols = 0 is
+ * hr_index_search in rows, order and fp32 score bits.  beta is always a HOST array.
+ * Mechanism (part of the contract: the stage that answers a query follows from it).
+ *   1 pilot   the exact search for P = probe rows; tau = the k-th largest true v among the pool's rows (rescored in
+ *             fp64; rows with a NaN v do not count), -inf when the pool holds fewer than k of them.
+ *   2 floor   bext_c = the largest value of column c over ALL rows [0, n) when beta[c] >= 0, the smallest when
+ *             beta[c] < 0 (dead, masked and never-set rows included; a device reduction cached on the handle until
+ *             the column is written or the index grows).  Vmax(x) = the blend with s := x and every b_c := bext_c.
+ *             Rounded products and sums are monotone in each operand, so v(r) <= Vmax(s(r)) and Vmax is
+ *             non-decreasing.  t0 = the smallest fp32 value with Vmax((double)t0) >= tau, by bisection over the
+ *             ordered fp32 bit patterns on the device; t = nextafterf(t0, -inf).  Every row with v(r) >= tau then
+ *             has (float)s(r) >= t; no slack constant.
+ *   3 window  (stage 1) the range search at min_score = t with max_hits = window.  A query whose exact hit count is
+ *             <= window has every candidate in hand: the window's rows are rescored (v), sorted by (v desc, row asc)
+ *             in LDS and the first k written.
+ *   4 all     (stage 2) a query whose count exceeds window, one at a time: the canonical score of every live,
+ *             allowed row, turned into v in place, the rows with v >= tau selected, a stable descending radix sort of
+ *             those rows only, the first k taken.  No n-row sort.
+ * Limits, all checked on the host before any launch (and before the handle is looked at): 1 <= k <= HR_MAX_K; alpha
+ * finite and in [2^-64, 2^64]; |beta[c]| <= 2^64, negative values are legal (a penalty); 0 <= n_cols <=
+ * HR_BOOST_MAX_COLS; probe = 0: the default min(HR_MAX_K, max(32, 4 k)), else k <= probe <= HR_MAX_K; window = 0: the
+ * default 4096, else k <= window <= HR_BOOST_MAX_WINDOW.  Any B >= 1, every dtype and metric; an empty index returns
+ * padding; a multi-device handle: HR_E_UNSUPPORTED; the mask follows the rules of hr_index_search.  The device form
+ * (q, mask and outputs in device memory) is ordered after the work queued on `stream` and returns with it idle. */
+#define HR_BOOST_MAX_COLS 4
+#define HR_BOOST_MAX_WINDOW 8192
+int hr_index_set_boost(hr_index* h, int col, int64_t row0, int64_t n, const float* values /* host */);
+int hr_index_search_boosted(hr_index* h, const float* q, int B, int k, double alpha,
+                            const double* beta /* n_cols, host */, int n_cols, int probe, int window,
+                            const uint64_t* row_mask, double* blended_out /* B*k */, float* scores_out /* B*k */,
+                            int64_t* rows_out /* B*k */);
+int hr_index_search_boosted_device(hr_index* h, const float* q_dev, int B, int k, double alpha,
+                                   const double* beta /* n_cols, host */, int n_cols, int probe, int window,
+                                   const uint64_t* row_mask_dev, double* blended_out_dev, float* scores_out_dev,
+                                   int64_t* rows_out_dev, void* stream);
 /* Search by example: queries built on the device from stored rows ("more like this chunk": Qdrant's recommend,
  * Weaviate's nearObject, Pinecone's query by id; tests/examples_ref.py restates it bit for bit).
  * A batch of B queries.  Query b has an optional fp32 base vector q[b] (q = NULL: none) and m_b = ex_off[b + 1] -

@@ -89,6 +89,11 @@ int hr_index_range_stats(hr_index* h, int64_t out[3]);
  * reports a FILTER's ([query group][wave], blocking; up to cap counts, the number in n_out). */
 int hr_index_range_wave_tiles(hr_index* h, uint32_t* out, int cap, int* n_out);
 
+/* Diagnostics of the boosted search (hr_index_search_boosted), cumulative: queries answered by stage 1, the window
+ * (out[0]), and by stage 2, the all-rows pass (out[1]); the queries of a call on an empty index count under out[0].
+ * The window is a range search: a boosted call also moves hr_index_range_stats' counters. */
+int hr_index_boost_stats(hr_index* h, int64_t out[2]);
+
 /* Diagnostics of the pipelined search: out[0] = caller host time per submit (us), out[1] = host time
  * per batch of the busiest shard thread (us), out[2] = batches submitted. */
 int hr_index_host_us(hr_index* h, double* out);

@@ -2932,6 +2932,7 @@ extern "C" void hr_index_destroy(hr_index* h) {
     if (h->norm_bits) (void)hipFree(h->norm_bits);
     collapse_free(h);
     range_free(h);
+    boost_free(h);
     mmr_free(h);
     examples_free(h);
     fused_free(h);

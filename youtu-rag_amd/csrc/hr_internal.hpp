@@ -1,6 +1,6 @@
 // hr_internal.hpp -- host-side internals shared by the libhiprag.so translation units
 // (hr_index.hip: index handles and the exact search; hr_ivf.hip: the IVF lists search; the derived searches
-// hr_collapse / hr_mmr / hr_range / hr_examples / hr_fuse .hip).  Shared here: the error macro, DevBuf and up256,
+// hr_collapse / hr_mmr / hr_range / hr_examples / hr_fuse / hr_boost .hip).  Shared here: the error macro, DevBuf and up256,
 // the index handle with its ONE host-form staging area (HostStage) and inner-search pool (pool_s / pool_r), the
 // staging helpers every host form is written in (stage_queries, stage_mask, stage_masks, stage_out /
 // stage_download), TileListScope, and the fp32 / int64 padding launcher (pad_results, hr_exhaustive.hip).
@@ -341,6 +341,18 @@ struct hr_index {
     // one call's group offsets and weights as one block, packed in fu_host and copied once
     DevBuf fu_list;
     std::vector<uint8_t> fu_host;
+    // ---- boosted search (hr_boost.hip): the boost columns -- one fp32 per row each, allocated by the first
+    // hr_index_set_boost of the column and grown by doubling on their own, as the group column: entries [0, boost_cap)
+    // exist, rows at or beyond it read 0.0.  boost_ext_*: the column's extrema over rows [0, n), valid while
+    // boost_ext_n == n (-1: the column was written).  Work buffers allocated by the first call that needs them:
+    // bst_win the window of one chunk of queries, bst_keys stage 2's keys / rows / fp32 scores / selection of ONE
+    // query (20 n bytes), bst_sort the selected rows being sorted
+    float* boost[HR_BOOST_MAX_COLS] = {nullptr, nullptr, nullptr, nullptr};
+    int64_t boost_cap[HR_BOOST_MAX_COLS] = {0, 0, 0, 0};
+    float boost_ext_lo[HR_BOOST_MAX_COLS] = {0.f, 0.f, 0.f, 0.f}, boost_ext_hi[HR_BOOST_MAX_COLS] = {0.f, 0.f, 0.f, 0.f};
+    int64_t boost_ext_n[HR_BOOST_MAX_COLS] = {-1, -1, -1, -1};
+    DevBuf bst_win, bst_keys, bst_sort, bst_tmp;
+    int64_t n_boost_window = 0, n_boost_all = 0;  // queries answered by stage 1 (window) / stage 2 (all rows)
 };
 
 // an internal stream of h: on h's CU mask when one is set (priority is then not available), else high priority or
@@ -417,6 +429,11 @@ int index_range_chunk(hr_index* h, const float* q_dev, int bc, const uint64_t* m
 int range_floors(const double* qerr, const float* min_score, int B, int Bp, double max_norm, double gamma, double u_x,
                  int metric, float* floor_q, hipStream_t st);
 void range_free(hr_index* h);  // hr_index_destroy's part
+// the range search itself (hr_range.hip), for the searches built on it (hr_boost.hip): queries, thresholds (no NaN),
+// mask and outputs on h's device; the caller holds h->mu with the device current; returns with st idle
+int range_impl(hr_index* h, const float* q_dev, int B, const float* t_dev, int max_hits, const uint64_t* mask_dev,
+               float* s_out, int64_t* r_out, int64_t* c_out, hipStream_t st);
+void boost_free(hr_index* h);  // hr_boost.hip: hr_index_destroy's part
 void mmr_free(hr_index* h);  // hr_mmr.hip: hr_index_destroy's part
 void examples_free(hr_index* h);  // hr_examples.hip: hr_index_destroy's part
 void fused_free(hr_index* h);  // hr_fuse.hip: hr_index_destroy's part

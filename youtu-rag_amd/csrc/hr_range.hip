@@ -268,8 +268,10 @@ int order_large_region(hr_index* h, const float2* buf, const uint64_t* keys, int
     return hits_sorted(h, k_sorted, r_sorted, m, t, max_hits, s_out, r_out, c_out, st);
 }
 
+}  // namespace
+
 // queries, thresholds (already validated), mask and outputs on h's device.  The caller holds h->mu with the device
-// current.  Returns with st idle.
+// current.  Returns with st idle.  (hr_internal.hpp: the boosted search's window is this call.)
 int range_impl(hr_index* h, const float* q_dev, int B, const float* t_dev, int max_hits, const uint64_t* mask_dev,
                float* s_out, int64_t* r_out, int64_t* c_out, hipStream_t st) {
     if (h->n_live == 0 || h->n <= 0) {  // empty index: counts 0 and padding
@@ -364,6 +366,8 @@ int range_impl(hr_index* h, const float* q_dev, int B, const float* t_dev, int m
     HIP_TRY(hipStreamSynchronize(st));
     return HR_OK;
 }
+
+namespace {
 
 int check_args(hr_index* h, int B, int max_hits) {
     if (h->G > 1) return set_err(HR_E_UNSUPPORTED, "range search needs a single-device handle");

@@ -22,6 +22,8 @@ METRICS = {"cosine": 0, "ip": 1, "dot": 1, "euclidean": 2, "l2": 2}
 HR_MAX_K = 128   # include/hiprag.h
 HR_MAX_KC = 256
 HR_RANGE_MAX_HITS = 65536  # largest max_hits of search_range
+HR_BOOST_MAX_COLS = 4  # boost columns of an index (set_boost / search_boosted)
+HR_BOOST_MAX_WINDOW = 8192  # largest window of search_boosted
 HR_EX_MAX = 32  # examples of one query of search_examples
 HR_EX_KEEP = 1  # search_examples flag: the examples stay candidates
 HR_FUSE_MAX_MEMBERS = 16  # lists of one group of search_fused / fuse_lists
@@ -69,6 +71,7 @@ EXPORTS = [
     "hr_index_search_mmr", "hr_index_search_mmr_device", "hr_index_set_mmr_timing", "hr_index_mmr_last_ms",
     "hr_index_search_range", "hr_index_search_range_device", "hr_index_range_stats",
     "hr_index_range_wave_tiles",
+    "hr_index_set_boost", "hr_index_search_boosted", "hr_index_search_boosted_device", "hr_index_boost_stats",
     "hr_index_build_queries", "hr_index_build_queries_device", "hr_index_search_examples",
     "hr_index_search_examples_device",
     "hr_fuse_lists", "hr_index_search_fused", "hr_index_search_fused_device",
@@ -233,6 +236,11 @@ def load_library(path: str | None = None):
             "hr_index_search_range_device": [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp],
             "hr_index_range_stats": [vp, vp],
             "hr_index_range_wave_tiles": [vp, vp, i32, vp],
+            "hr_index_set_boost": [vp, i32, i64, i64, vp],
+            "hr_index_search_boosted": [vp, vp, i32, i32, ctypes.c_double, vp, i32, i32, i32, vp, vp, vp, vp],
+            "hr_index_search_boosted_device": [vp, vp, i32, i32, ctypes.c_double, vp, i32, i32, i32, vp, vp, vp, vp,
+                                               vp],
+            "hr_index_boost_stats": [vp, vp],
             "hr_index_build_queries": [vp, vp, vp, vp, i32, vp, vp],
             "hr_index_build_queries_device": [vp, vp, vp, vp, i32, vp, vp, vp],
             "hr_index_search_examples": [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp],
@@ -598,6 +606,57 @@ class NativeIndex:
         n = ctypes.c_int(0)
         _check(self.lib.hr_index_range_wave_tiles(self._h, _ptr(out), int(cap), ctypes.byref(n)))
         return out[: n.value].copy()
+
+    # -- boosted search (hr_boost.hip): the exact top-k of alpha * similarity + sum of beta_c * boost column c
+    def set_boost(self, col: int, row0: int, values) -> None:
+        """fp32 boost values (finite) of rows [row0, row0 + len(values)) of column ``col`` (hr_index_set_boost)."""
+        v = np.ascontiguousarray(np.asarray(values, np.float32).reshape(-1))
+        _check(self.lib.hr_index_set_boost(self._h, int(col), int(row0), len(v), _ptr(v)))
+
+    @staticmethod
+    def _betas(betas) -> np.ndarray:
+        b = np.ascontiguousarray(np.asarray(betas, np.float64).reshape(-1))
+        if len(b) > HR_BOOST_MAX_COLS:
+            raise ValueError(f"at most {HR_BOOST_MAX_COLS} boost columns")
+        return b
+
+    def search_boosted(self, q: np.ndarray, k: int, alpha: float, betas, mask: np.ndarray | None = None,
+                       probe: int = 0, window: int = 0) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """The first ``k`` live, allowed rows by ``alpha * score + sum_c betas[c] * column_c`` (fp64, every operation
+        rounded once, in column order), then row ascending -- over the whole index, exactly
+        (hr_index_search_boosted): ``(blended f64, scores f32, rows i64)``, the scores being search()'s; -inf / -inf /
+        -1 past the live, allowed rows.  ``probe`` / ``window``: the pilot's depth and the stage-1 window (0 = the
+        library's defaults)."""
+        q = self._queries(q)
+        B = q.shape[0]
+        if int(k) <= 0 or int(k) > HR_MAX_K:  # (before the output arrays are sized by it)
+            raise ValueError(f"k must be in [1, {HR_MAX_K}]")
+        b = self._betas(betas)
+        v = np.empty((B, int(k)), np.float64)
+        s = np.empty((B, int(k)), np.float32)
+        r = np.empty((B, int(k)), np.int64)
+        m = self._mask_words(mask)
+        _check(self.lib.hr_index_search_boosted(self._h, _ptr(q), B, int(k), float(alpha), _ptr(b) if len(b) else None,
+                                                len(b), int(probe), int(window), _ptr(m), _ptr(v), _ptr(s), _ptr(r)))
+        return v, s, r
+
+    def search_boosted_device(self, q_ptr: int, B: int, k: int, alpha: float, betas, blended_ptr: int,
+                              scores_ptr: int, rows_ptr: int, mask_ptr: int = 0, probe: int = 0, window: int = 0,
+                              stream: int = 0) -> None:
+        """search_boosted() with the queries, the mask and the three outputs in device memory (``betas`` stays a host
+        sequence); ordered after the work queued on ``stream``, which is idle on return."""
+        b = self._betas(betas)
+        _check(self.lib.hr_index_search_boosted_device(self._h, ctypes.c_void_p(q_ptr), int(B), int(k), float(alpha),
+                                                       _ptr(b) if len(b) else None, len(b), int(probe), int(window),
+                                                       ctypes.c_void_p(mask_ptr or None),
+                                                       ctypes.c_void_p(blended_ptr), ctypes.c_void_p(scores_ptr),
+                                                       ctypes.c_void_p(rows_ptr), ctypes.c_void_p(stream or None)))
+
+    def boost_stats(self) -> dict:
+        """Cumulative boosted queries answered by the window (stage 1) / by the all-rows pass (stage 2)."""
+        out = (ctypes.c_int64 * 2)()
+        _check(self.lib.hr_index_boost_stats(self._h, out))
+        return {"window": int(out[0]), "all_rows": int(out[1])}
 
     # -- search by example (hr_examples.hip): queries built on the device from stored rows
     @staticmethod

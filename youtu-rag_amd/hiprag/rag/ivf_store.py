@@ -220,6 +220,17 @@ class IvfStoreIndex:
     def range_stats(self) -> dict:
         return self.exact.range_stats()
 
+    # a boosted answer is exact over the whole collection by definition: the exact index holds the boost columns
+    def set_boost(self, col: int, row0: int, values) -> None:
+        self.exact.set_boost(col, row0, values)
+
+    def search_boosted(self, q: np.ndarray, k: int, alpha: float, betas, mask: np.ndarray | None = None,
+                       probe: int = 0, window: int = 0):
+        return self.exact.search_boosted(q, k, alpha, betas, mask, probe, window)
+
+    def boost_stats(self) -> dict:
+        return self.exact.boost_stats()
+
     # ---------------------------------------------------------------- persistence
     def save(self, path: str) -> None:
         """The exact index to ``path`` as ever, and ``path + ".ivf.npz"``: centroids, nlist, the seed, the list of

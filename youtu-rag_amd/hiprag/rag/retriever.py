@@ -327,6 +327,35 @@ class VectorRetriever(BaseRetriever):
                    for pos, (chunk, score) in enumerate(found.hits)]
         return await self._finish(query, results, int(limit))
 
+    async def retrieve_boosted(self, query: str, top_k: int | None = None, *, boost_weights: dict,
+                               sim_weight: float = 1.0, filters: dict | None = None,
+                               similarity_threshold: float | None = None) -> list[RetrievalResult]:
+        """The ``top_k`` chunks by ``sim_weight * similarity + sum of boost_weights[f] * metadata[f]`` over the whole
+        collection -- the store's boosted search (``index_params.boost_fields``), not a re-ranking of a guessed
+        similarity window.  ``score`` is the blended value; ``similarity_threshold`` (default
+        ``config.similarity_threshold``, <= 0 disables it as in retrieve()) cuts by the SIMILARITY of a hit, so it
+        keeps its meaning whatever the weights.  Ranks are 1-based, before the cut; the optional reranker and the
+        final cut apply as in retrieve().
+
+        The reference's memory ranking (memory_toolkit.py:919), ``0.5 * similarity + 0.3 * importance_score + 0.2 *
+        recency`` with ``recency = 2 ** (-(now - created_at) / 24h)``, needs no column rewrite as time passes: store
+        ``importance_score`` and the static ``recency_base = 2 ** ((created_at - epoch) / 24h)`` as boost fields; the
+        query-time factor ``2 ** (-(now - epoch) / 24h)`` folds into that column's weight:
+        ``boost_weights={"importance_score": 0.3, "recency_base": 0.2 * 2 ** (-(now - epoch) / 24h)}, sim_weight=0.5``
+        (choose ``epoch`` near the newest memories so that ``recency_base`` stays inside float32)."""
+        search_boosted = getattr(self.vector_store, "search_boosted", None)
+        if search_boosted is None:
+            raise NotImplementedError(f"{type(self.vector_store).__name__} has no boosted search")
+        top_k = top_k or self.config.top_k
+        threshold = self.config.similarity_threshold if similarity_threshold is None else similarity_threshold
+        qv = await self.embedder.embed_query(query)
+        found = await search_boosted(query_embedding=qv, top_k=top_k * 2 if self.reranker else top_k,
+                                     boost_weights=boost_weights, sim_weight=sim_weight, filters=filters)
+        results = [RetrievalResult(chunk=chunk, score=float(v), rank=pos + 1)
+                   for pos, ((chunk, sim), v) in enumerate(zip(found.hits, found.blended))
+                   if not (threshold > 0 and sim < threshold)]
+        return await self._finish(query, results, top_k)
+
     async def retrieve_similar(self, chunk_id_or_ids, top_k: int | None = None, filters: dict | None = None,
                                negative_ids=None, query: str | None = None) -> list[RetrievalResult]:
         """"More like this chunk": the store's search by example over the stored vectors of ``chunk_id_or_ids`` (one

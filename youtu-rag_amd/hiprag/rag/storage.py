@@ -80,6 +80,15 @@ a ``FusedHits(hits, members)``: the (Chunk, fused score) pairs and per hit the b
 found it.  An index without a native ``search_fused`` (several devices, IVF_FLAT) gets the same arithmetic composed on
 the host from ``search``.  Calls do not go through the micro-batcher; the single-group form runs in a worker thread.
 
+Boosted search (``index_params.boost_fields``: up to four numeric metadata keys; ``search_boosted_batch(qs, top_k,
+boost_weights={field: weight}, sim_weight=1.0)`` / ``await search_boosted``; single device): the ``top_k`` chunks by
+``sim_weight * similarity + sum of weight * field`` over the whole collection, exactly -- importance, recency or
+popularity blended into the ranking, not a re-ranking of a guessed similarity window (hr_index_search_boosted;
+DESIGN.md 4m).  The fields' values live in boost columns on the index, built lazily from the metadata tables (missing,
+non-numeric and non-finite values are 0.0) and never persisted.  Each query gets a ``BoostedHits(hits, blended)``: the
+(Chunk, similarity) pairs in blended order and the blended values.  Calls do not go through the micro-batcher; the
+single-query form runs in a worker thread.
+
 ``index_type: "IVF_FLAT"`` (any letter case; single device, cosine / dot): the index is an ``IvfStoreIndex``
 (ivf_store.py) -- the same exact index plus an IVF replica that answers searches once ``ivf_train_rows`` live rows
 are stored (``index_params``: nlist, nprobe, ivf_train_rows = 64 nlist, ivf_seed).  It comes in through the
@@ -92,6 +101,7 @@ import asyncio
 import contextlib
 import json
 import logging
+import math
 import os
 import threading
 from array import array
@@ -107,6 +117,8 @@ from .base import BaseVectorStore, Chunk
 from .lexical import MAX_K as _LEX_MAX_K, LexicalIndex
 from .config import VectorStoreConfig
 from .ivf_store import IvfStoreIndex, wants_ivf
+
+_F32_MAX = float(np.finfo(np.float32).max)  # boost values beyond it are no float32: they count as 0.0
 
 try:  # the per-hit result assembly in C (csrc/host/hostfast.c, built by csrc/Makefile); host-side only, same output
     from . import _hostfast
@@ -248,6 +260,13 @@ class RangeHits(NamedTuple):
     def truncated(self) -> bool:
         """More rows reached the threshold than ``hits`` holds."""
         return self.total > len(self.hits)
+
+
+class BoostedHits(NamedTuple):
+    """One query's answer to a boosted search: its (Chunk, similarity) pairs ordered by the blended value, best first,
+    and per hit that blended value (``sim_weight * similarity + sum of boost_weights[f] * f``, float64)."""
+    hits: list
+    blended: list
 
 
 class _ObjColumn:
@@ -557,6 +576,10 @@ class HipVectorStore(BaseVectorStore):
         self.capacity = int(params.get("capacity", 0))
         # collapsed search: what a row groups by -- its document_id, or this metadata key (document_id where absent)
         self.collapse_field = str(params.get("collapse_field", "document_id"))
+        # boosted search: the metadata keys (at most 4) whose numeric values are the index's boost columns, in order
+        self.boost_fields = [str(f) for f in params.get("boost_fields") or []]
+        if len(self.boost_fields) > _native.HR_BOOST_MAX_COLS or len(set(self.boost_fields)) != len(self.boost_fields):
+            raise ValueError(f"index_params.boost_fields takes at most {_native.HR_BOOST_MAX_COLS} distinct keys")
         self.include_embeddings = bool(params.get("include_embeddings", False))
         self.keep_embeddings = bool(params.get("keep_embeddings", False))
         # returned Chunks with atomic-valued metadata left off the cycle collector (faster under heavy load; a cycle
@@ -626,6 +649,10 @@ class HipVectorStore(BaseVectorStore):
         self._group_ids: dict | None = None
         self._group_col = np.zeros(0, np.int32)
         self._group_rows = self._group_sent = 0
+        # boosted search, built at the first one (_ensure_boosts): the host columns (one float32 row of this array per
+        # boost field, 0.0 for a dead row or a value that is no finite number) and how many rows the index holds
+        self._boost_cols: np.ndarray | None = None
+        self._boost_rows = self._boost_sent = 0
 
     # ---------------------------------------------------------------- persistence
     def _load_if_present(self):
@@ -809,6 +836,8 @@ class HipVectorStore(BaseVectorStore):
         self._lex_append(first, [None if rec is None else rec["content"] for rec in records])
         if self._group_ids is not None:
             self._extend_groups(len(self._records))
+        if self._boost_cols is not None:
+            self._extend_boosts(len(self._records))
         n = len(self._records)
         if len(self._live) < n:
             live = np.zeros(max(n, 2 * len(self._live), 1024), bool)
@@ -862,6 +891,45 @@ class HipVectorStore(BaseVectorStore):
         if self._group_sent < n:
             self._index.set_groups(self._group_sent, self._group_col[self._group_sent:n])
             self._group_sent = n
+
+    def _extend_boosts(self, n: int):
+        """Boost values of rows [_boost_rows, n) into the host columns (store lock held): bool / int / float metadata
+        values as float32; a missing, non-numeric or non-finite one (also one beyond float32) is 0.0."""
+        first = self._boost_rows
+        if n <= first:
+            return
+        if self._boost_cols.shape[1] < n:
+            cols = np.zeros((len(self.boost_fields), max(n, 2 * self._boost_cols.shape[1], 1024)), np.float32)
+            cols[:, :first] = self._boost_cols[:, :first]
+            self._boost_cols = cols
+        for row in range(first, n):
+            meta = self._metas[row] if self._records[row] is not None else None
+            for c, field in enumerate(self.boost_fields):
+                v = (meta or {}).get(field)
+                x = 0.0
+                if isinstance(v, (bool, int, float)):
+                    try:
+                        x = float(v)
+                    except OverflowError:
+                        x = 0.0
+                    if not math.isfinite(x) or abs(x) > _F32_MAX:
+                        x = 0.0
+                self._boost_cols[c, row] = x
+        self._boost_rows = n
+
+    def _ensure_boosts(self):
+        """The boost columns current on the host and on the device (store lock held, an index present): built from the
+        metadata tables at the first boosted search -- after a reload too, nothing of them is persisted -- then
+        extended by _append_tables; the rows the index has not seen yet go up here."""
+        n = len(self._records)
+        if self._boost_cols is None:
+            self._boost_cols = np.zeros((len(self.boost_fields), 0), np.float32)
+            self._boost_rows = self._boost_sent = 0
+        self._extend_boosts(n)
+        if self._boost_sent < n:
+            for c in range(len(self.boost_fields)):
+                self._index.set_boost(c, self._boost_sent, self._boost_cols[c, self._boost_sent:n])
+            self._boost_sent = n
 
     def _lex_append(self, first: int, contents: list):
         """The same rows into the lexical index (None: a dead row -- it takes its row number and no terms)."""
@@ -1501,6 +1569,98 @@ class HipVectorStore(BaseVectorStore):
         q = np.asarray(query_embedding, dtype=np.float32).reshape(1, -1)
         prep = self._prep_range(q, min_score, max_hits, filters)  # checked here: a bad request fails alone
         return self._range_hits(prep, await asyncio.to_thread(self._run_range, prep))[0]
+
+    # -- boosted search (hr_index_search_boosted): similarity blended with per-row metadata boosts
+    def _prep_boosted(self, query_embeddings, top_k: int, boost_weights, sim_weight, filters, probe, window):
+        """(q, k, alpha, betas, filters, probe, window) of a boosted search, every limit checked: a bad request fails
+        here, before any native call.  betas: one weight per configured boost field, 0.0 for a field not named."""
+        q = _as_queries(query_embeddings, self.dim)
+        k = int(top_k)
+        if k < 1 or k > _native.HR_MAX_K:
+            raise ValueError(f"top_k must be in [1, {_native.HR_MAX_K}] (got {k})")
+        alpha = float(sim_weight)
+        if not (2.0 ** -64 <= alpha <= 2.0 ** 64):
+            raise ValueError(f"sim_weight must be in [2**-64, 2**64] (got {sim_weight})")
+        if not isinstance(boost_weights, dict):
+            raise ValueError("boost_weights must be a dict of boost field -> weight")
+        betas = [0.0] * len(self.boost_fields)
+        for name, w in boost_weights.items():
+            if name not in self.boost_fields:
+                raise ValueError(f"{name!r} is not a configured boost field (index_params.boost_fields = "
+                                 f"{self.boost_fields})")
+            w = float(w)
+            if not abs(w) <= 2.0 ** 64:
+                raise ValueError(f"boost weight of {name!r} must be finite and at most 2**64 in size (got {w})")
+            betas[self.boost_fields.index(name)] = w
+        probe = 0 if probe is None else int(probe)
+        if probe != 0 and not k <= probe <= _native.HR_MAX_K:
+            raise ValueError(f"probe must be in [top_k, {_native.HR_MAX_K}] (got {probe})")
+        window = 0 if window is None else int(window)
+        if window != 0 and not k <= window <= _native.HR_BOOST_MAX_WINDOW:
+            raise ValueError(f"window must be in [top_k, {_native.HR_BOOST_MAX_WINDOW}] (got {window})")
+        filters = _per_query_filters(filters, q.shape[0])
+        if not self._single_device(self._index):
+            raise ValueError("a boosted search needs a single-device store")
+        return q, k, alpha, betas, filters, probe, window
+
+    def _run_boosted(self, prep):
+        """The native boosted search under the store lock, as _run_range: ((scores, rows) or None, blended, tables).
+        The boost columns are brought up to date under the same lock hold.  A per-query filter list runs one call per
+        distinct where-clause, scattered back in query order."""
+        q, k, alpha, betas, filters, probe, window = prep
+        with self._lock:  # ordered against mutations
+            tables = self._tables()
+            idx = self._index
+            if idx is None or self.count_sync() == 0:
+                return None, None, tables
+            if not self._single_device(idx):
+                raise ValueError("a boosted search needs a single-device store")
+            if not hasattr(idx, "search_boosted") or not hasattr(idx, "set_boost"):
+                raise NotImplementedError(f"{type(idx).__name__} has no boosted search")
+            self._ensure_boosts()
+            if not isinstance(filters, list):
+                v, s, r = idx.search_boosted(q, k, alpha, betas, self.filter_bitmap(filters), probe, window)
+                return (s, r), np.asarray(v, np.float64), tables
+            blended = np.full((q.shape[0], k), -np.inf, np.float64)
+
+            def call(sel, bitmap):
+                blended[sel], s, r = idx.search_boosted(q[sel], k, alpha, betas, bitmap, probe, window)
+                return s, r
+
+            return self._per_clause(self._distinct_filters(filters), k, call), blended, tables
+
+    def _boosted_hits(self, prep, ran) -> list[BoostedHits]:
+        raw, blended, tables = ran
+        g = None if raw is None else self._gather((raw, tables), extra=blended)
+        if g is None:
+            return [BoostedHits([], []) for _ in range(len(prep[0]))]
+        rec_l, meta_l, score_l, per_q, embs, bl_l = g
+        out, i = [], 0
+        for hits, cnt in zip(_assemble_py(Chunk, rec_l, meta_l, score_l, per_q, embs), per_q):
+            # (a hit deleted since the search ran is dropped, and its blended value with it)
+            out.append(BoostedHits(hits, [v for r, v in zip(rec_l[i:i + cnt], bl_l[i:i + cnt]) if r is not None]))
+            i += cnt
+        return out
+
+    def search_boosted_batch(self, query_embeddings, top_k: int = 5, *, boost_weights: dict, sim_weight: float = 1.0,
+                             filters=None, probe: int | None = None, window: int | None = None) -> list[BoostedHits]:
+        """The ``top_k`` chunks by ``sim_weight * similarity + sum of boost_weights[f] * metadata[f]`` over the WHOLE
+        collection, exactly -- not a re-ranking of a guessed similarity window (hr_index_search_boosted).  The fields
+        are those of ``index_params.boost_fields`` (numeric metadata; missing, non-numeric or non-finite values count
+        as 0.0); a negative weight is a penalty.  Per query a BoostedHits: the (Chunk, similarity) pairs in blended
+        order, and the blended values.  ``filters``: one where-clause, or a list with one (or None) per query;
+        ``probe`` / ``window``: the native call's pilot depth and stage-1 window (None: its defaults)."""
+        prep = self._prep_boosted(query_embeddings, top_k, boost_weights, sim_weight, filters, probe, window)
+        return self._boosted_hits(prep, self._run_boosted(prep))
+
+    async def search_boosted(self, query_embedding: list[float], top_k: int = 5, *, boost_weights: dict,
+                             sim_weight: float = 1.0, filters: dict[str, Any] | None = None,
+                             probe: int | None = None, window: int | None = None) -> BoostedHits:
+        """One query's boosted search, off the event loop (a boosted call is two corpus passes of its own, not a
+        micro-batched top-k)."""
+        q = np.asarray(query_embedding, dtype=np.float32).reshape(1, -1)
+        prep = self._prep_boosted(q, top_k, boost_weights, sim_weight, filters, probe, window)  # a bad request fails alone
+        return self._boosted_hits(prep, await asyncio.to_thread(self._run_boosted, prep))[0]
 
     # -- search by example (hr_index_search_examples; DESIGN.md 4k): "more like these chunks"
     def _prep_similar(self, positive_ids, negative_ids, top_k: int, filters, query_embeddings, pos_weight, neg_weight):
